@@ -1,10 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the multiview feature -> voxel projection + aggregation path on MI355X.
 
-    python bench.py                                   # 1 GPU, BASELINE.json configs[1]
+    python bench.py                                   # 1 GPU, BASELINE.json configs[1]: the headline figure only
     python bench.py --gpus N [--steps K --warmup W]   # N > 1 without torchrun: bench.py spawns the N ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W        # or under a launcher (RANK / LOCAL_RANK / WORLD_SIZE in the env)
+    python bench.py --full                            # + roofline, kernel table, side legs, cpu_baseline
+    python bench.py --dump-outputs bench_outputs      # + the last timed step's BEV map as bench_outputs/ortho.npy
+
+A plain run sets up, warms up (`--warmup` steps, then the `--condition-steps` lead-in), times EXACTLY `--steps` steps in one block
+and prints the headline line (`value`, `ms_per_step`, ...).  `--full` adds everything else this file measures: the headline block is
+then repeated until >= 100 ms are timed (median block) with HIP events around sampled launches for `roofline` / `kernels`, and the
+side legs below run after it.
 
 One step = one pass of the hot path over one synthetic frame already resident in HBM: for each of the three feature
 scales the integral images of the local cameras, projection + box pooling and the collapse (Linear + bias + ReLU + view
@@ -16,9 +23,9 @@ Workload and scaling.  The primary line is `multiviewc_200x200x1` (BASELINE.json
 scaling, the north-star partitioning: the 7 cameras of each frame are sharded over the ranks (one camera per GPU at
 N >= 7; a rank without a camera contributes zeros), the partial maps are fused by one RCCL all-reduce over xGMI, frames
 are streamed and the all-reduce of frame i overlaps the projection of frame i+1.  The same line also carries
-`scaling_curve_c5`: BASELINE.json configs[4] (`synthetic4k_512x512x32`, 8 cameras x 4K, one camera per GPU at N = 8),
+`scaling_curve_c5` (`--full`): BASELINE.json configs[4] (`synthetic4k_512x512x32`, 8 cameras x 4K, one camera per GPU at N = 8),
 measured the same way with fewer steps -- the configuration on which >= 6x at 8 GPUs is attainable.
-`--scaling weak` (every rank a full rig, grids summed) is kept as an option.  Side legs at N = 1 (none of them `value`):
+`--scaling weak` (every rank a full rig, grids summed) is kept as an option.  Side legs at N = 1 (`--full`; none of them `value`):
 `shipped_configs` (the reference's three shipped configs through the pipelined kernel), `training_step` (forward + backward of the
 bench frame through the fused autograd node), `per_rank_proxy`, `reference_loop`, `producer_f3`, the other arithmetic forms.
 
@@ -45,13 +52,20 @@ SHIPPED = ("multiviewc_156x156x5", "wildtrack_120x360x8", "multiviewx_160x250x8"
 # algorithmic bytes per frame (feature maps read once + voxel features written once + the map)
 SURVEY_ALG_BYTES = {"multiviewc_156x156x5": 3.03e9, "multiviewc_200x200x1": 1.28e9, "wildtrack_120x360x8": 7.85e9,
                     "wildtrack_480x1440x1": 15.95e9, "multiviewx_160x250x8": 6.26e9, "synthetic4k_512x512x32": 210.4e9}
+DUMP_BYTES = 60 << 20  # --dump-outputs writes at most this much (the bench frame's map is 41 MB)
 
 
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=200)
+    p.add_argument("--steps", type=int, default=200,
+                   help="timed steps (with --full: steps per timed block, the block repeated until >= 100 ms are timed)")
     p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline figure: roofline and kernel table, side legs, CPU baseline, multi-GPU collectives")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the BEV map of the last timed step (rank 0) as DIR/ortho.npy, float32 (a fixed, seeded sample of "
+                        f"its elements when it exceeds {DUMP_BYTES >> 20} MiB)")
     p.add_argument("--condition-steps", type=int, default=150,
                    help="untimed frames queued right in front of the opening barrier + synchronize of a timed region, so that a "
                         "short run does not measure the clock ramp of an idle device (0 disables)")
@@ -98,6 +112,22 @@ def spawn_ranks(n):
     sys.stdout.write(out.decode())
     sys.stdout.flush()
     return max(abs(c) for c in codes)
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs`: every tensor of `arrays` as out_dir/<name>.npy in float32, in the shape the caller receives it.  Together they
+    stay under DUMP_BYTES: a larger tensor is written as a flat sample of its elements whose positions come from a fixed seed, the
+    same in every run and every build."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // max(len(arrays), 1) // 4
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > budget:
+            pos = torch.randint(t.numel(), (budget,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[pos.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def cpu_model():
@@ -207,6 +237,7 @@ class Leg:
         # in flight); every collective completes inside the timed region.  VFA_BENCH_SYNC_REDUCE=1 reduces synchronously.
         self.overlap = world > 1 and os.environ.get("VFA_BENCH_SYNC_REDUCE", "0") != "1"
         self.pending = []
+        self.last = None
         self.k = 0
         self.collective = True  # (False: the same steps without the collective: per-rank compute time)
         self.mode = getattr(a, "collective", "reduce")  # "reduce" -> rank 0 or "all_reduce"
@@ -215,12 +246,15 @@ class Leg:
         torch, vfa_amd = self.torch, self.vfa_amd
         lats = self.sets[self.k % len(self.sets)]
         self.k += 1
+        self.last = None  # (`last`: the map of the latest finished frame; released before the next one is allocated)
         with torch.no_grad():
             if not self.collective:
-                return vfa_amd.aggregate_views(*self.mods, *lats, self.calibs, self.grid, distributed=False)
+                self.last = vfa_amd.aggregate_views(*self.mods, *lats, self.calibs, self.grid, distributed=False)
+                return self.last
             if not self.overlap:
                 how = ("reduce" if self.mode == "reduce" else True) if self.world > 1 else False
-                return vfa_amd.aggregate_views(*self.mods, *lats, self.calibs, self.grid, distributed=how)
+                self.last = vfa_amd.aggregate_views(*self.mods, *lats, self.calibs, self.grid, distributed=how)
+                return self.last
             while self.pending:
                 self.pending.pop().wait()  # frame i-1 is fused before frame i's collective is queued
             self.pending.append(vfa_amd.aggregate_views(*self.mods, *lats, self.calibs, self.grid,
@@ -228,7 +262,7 @@ class Leg:
 
     def drain(self):
         while self.pending:
-            self.pending.pop().wait()
+            self.last = self.pending.pop().wait()
 
     def fence(self):
         if self.world > 1:
@@ -548,6 +582,18 @@ def main():
     # driver's 20 steps are 13 ms) would measure the ramp, not the path: a fixed number of untimed frames are queued right in
     # front of the opening bracket of every timed region (`Leg.timed`), the same on every rank.
     conditioning = 0 if a.steps <= 0 else max(0, int(a.condition_steps))
+    primary_terms = 2 if vfa_op.COLLAPSE_TERMS in (0, 2) or (leg.nl == 1 and vfa_op.COLLAPSE_TERMS == 6) else vfa_op.COLLAPSE_TERMS
+    if not a.full:
+        # the headline figure alone: the warm-up, then exactly `--steps` steps in ONE bracketed block, no HIP events inside it
+        for _ in range(a.warmup):
+            leg.step()
+        leg.drain()
+        leg.fence()
+        dt = leg.timed(a.steps, lead_in=conditioning)
+        if rank == 0 and a.dump_outputs:
+            dump_outputs(a.dump_outputs, {"ortho": leg.last})
+        finish(world, dist, headline(a, leg, dt, world, scaling, conditioning, primary_terms) if rank == 0 else None)
+        return
     # Warm-up steps: HIP events around EVERY entry point (the `kernels` table).  Timed steps: only around the roofline
     # kernel, sampled -- each timed launch puts two event records in the queue (~3 us apiece).
     with ops.KernelTimer() as kt_warm:
@@ -565,10 +611,11 @@ def main():
     # rooflines come from the region `value` is measured in, not from the warm-up)
     kt = ops.KernelTimer(every=4 if a.steps >= 8 else 1)
     dt = leg.timed(a.steps, kt, lead_in=conditioning, min_ms=min_ms)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"ortho": leg.last})
     timing = leg.block_stats(a.steps)
     ks = kt.summary()
     live = live_products(leg, ops, _lib)
-    primary_terms = 2 if vfa_op.COLLAPSE_TERMS in (0, 2) or (leg.nl == 1 and vfa_op.COLLAPSE_TERMS == 6) else vfa_op.COLLAPSE_TERMS
     roofline = roofline_of(ks, ops, a.workload, live, terms=primary_terms)
     if roofline is not None:
         roofline["sampled"] = (f"HIP events around every {kt.every}th launch of the timed region ({roofline['launches']} samples over "
@@ -950,28 +997,14 @@ def main():
 
     out = None
     if rank == 0:
-        out = {
-            "metric": "voxels aggregated/sec (7 views->BEV grid)", "value": leg.units_step * a.steps / dt,
-            "unit": "voxels/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "lead_in_frames": conditioning,  # untimed frames queued in front of the opening barrier + synchronize (clock ramp of an idle device)
-            "ms_per_step": 1e3 * dt / a.steps, "timing": timing, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
+        out = headline(a, leg, dt, world, scaling, conditioning, primary_terms)
+        out.update({
+            "timing": timing,
             "dtype_note": "fp32 in / out, fp32 accumulation everywhere.  Pre-GEMM: the reference's exact fp32 rounding sequence (the fused "
                           "kernels' pooled rows -- tap chains, box sum, correctly rounded quotient -- are the reference's voxel features bit for bit: tests/test_fused_frame.py). "
                           "The collapse product (reference: fp32 nn.Linear) = " + ARITHMETIC[primary_terms][3] + ".  Extra keys: "
                           "`bf16x2_16bit` = the narrower two-piece bf16 product (the default until round 3; NOT reference width), "
                           "`bf16x3_six_products` = three bf16 pieces, `collapse_fp32_ms_per_step` = the unfused step with the fp32 library GEMM",
-            "arithmetic": ARITHMETIC[primary_terms][0],
-            "config": {"workload": a.workload, "cameras_per_rank": n,
-                       "cameras_total": n * world if scaling == "weak" else leg.n_frame, "channels": C,
-                       "feature_maps": [list(s) for s in leg.wl["feat_sizes"]], "grid": [L, W, nl],
-                       "units_per_step": leg.units_step,
-                       "rccl_ranks": dist.get_world_size() if world > 1 else 1,
-                       "parallelism": (f"camera-sharded dp{world} ({scaling}), RCCL "
-                                       + ("reduce of the BEV map onto rank 0" if leg.mode == "reduce" else "all-reduce of the BEV map")
-                                       + (" overlapped with the next frame" if leg.overlap else "")) if world > 1
-                       else "single GPU",
-                       **({"collective": leg.mode} if world > 1 else {})},
             "bev_cells_per_s": nl * L * W * a.steps / dt,
             "roofline": roofline,
             "roofline_integral": integral_roofline,
@@ -980,14 +1013,42 @@ def main():
                             "TIMED blocks (the geometry calls run on a second stream beside the integral images)",
             "hip_kernel_ms_per_step": hip_ms,
             "collapse_gemm": collapse_info,
-        }
+        })
         out.update(extra)
         if world == 1 and a.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(leg.wl, a.cpu_seconds)
+    finish(world, dist, out)
+
+
+def headline(a, leg, dt, world, scaling, conditioning, terms):
+    """The keys of the result line that a plain run prints too: the headline figure and what it was measured on."""
+    n = len(leg.cams)
+    return {
+        "metric": "voxels aggregated/sec (7 views->BEV grid)", "value": leg.units_step * a.steps / dt,
+        "unit": "voxels/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "lead_in_frames": conditioning,  # untimed frames queued in front of the opening barrier + synchronize (clock ramp of an idle device)
+        "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "arithmetic": ARITHMETIC[terms][0],
+        "config": {"workload": a.workload, "cameras_per_rank": n,
+                   "cameras_total": n * world if scaling == "weak" else leg.n_frame, "channels": a.channels,
+                   "feature_maps": [list(s) for s in leg.wl["feat_sizes"]], "grid": [leg.L, leg.W, leg.nl],
+                   "units_per_step": leg.units_step,
+                   "rccl_ranks": world,
+                   "parallelism": (f"camera-sharded dp{world} ({scaling}), RCCL "
+                                   + ("reduce of the BEV map onto rank 0" if leg.mode == "reduce" else "all-reduce of the BEV map")
+                                   + (" overlapped with the next frame" if leg.overlap else "")) if world > 1
+                   else "single GPU",
+                   **({"collective": leg.mode} if world > 1 else {})},
+    }
+
+
+def finish(world, dist, out):
+    """Closes the process group and prints the result line (rank 0 only: `out` is None on the other ranks)."""
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0:
+    if out is not None:
         print(json.dumps(out))
 
 

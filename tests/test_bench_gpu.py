@@ -28,7 +28,7 @@ def test_bench_spawns_its_own_ranks_and_shards_cameras():
     """`python bench.py --gpus 2` without a launcher must run TWO ranks (the driver calls it exactly like this).  On a
     1-GPU box both ranks share device 0 and the collective runs over gloo (functional check only, never a number)."""
     two_gpus = torch.cuda.device_count() >= 2
-    p = _run(["--gpus", "2"] + FAST, env={} if two_gpus else {"VFA_BENCH_BACKEND": "gloo"})
+    p = _run(["--gpus", "2", "--full"] + FAST, env={} if two_gpus else {"VFA_BENCH_BACKEND": "gloo"})
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["config"]["rccl_ranks"] == 2 and line["config"]["collective"] == "reduce"
@@ -57,7 +57,7 @@ def test_two_rank_rccl_sum_matches_single_gpu():
 
 
 def test_bench_single_gpu_line_has_the_contract_fields():
-    p = _run(["--steps", "5", "--warmup", "2", "--c5-steps", "0", "--cpu-seconds", "2", "--rotate", "2", "--fp32-steps", "2", "--proxy-steps", "2"])
+    p = _run(["--full", "--steps", "5", "--warmup", "2", "--c5-steps", "0", "--cpu-seconds", "2", "--rotate", "2", "--fp32-steps", "2", "--proxy-steps", "2"])
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -89,3 +89,36 @@ def test_bench_single_gpu_line_has_the_contract_fields():
     ts = line["training_step"]  # forward + backward of the bench frame through the fused autograd node (f2)
     assert ts["ms_per_step"] > 0 and ts["steps"] == 5 and "vfa_project_gather_backward_grid_f32" in ts["entry_points_ms_per_step"]
     assert "vfa_collapse_gemm_relu_backward_f16_f32" in ts["entry_points_ms_per_step"]
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: exactly K timed steps, the headline keys only, and with --dump-outputs the BEV
+    map of the last timed step -- what aggregate_views returns for the bench's seeded inputs, recomputed here."""
+    import numpy as np
+    import vfa_amd
+    from vfa_amd.synthetic import make_workload
+    out_dir = tmp_path / "outputs"
+    p = _run(["--steps", "3", "--warmup", "1", "--dump-outputs", str(out_dir)])
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = p.stdout.strip().splitlines()
+    assert len(lines) == 1 and len(lines[0]) < 4096
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "voxels/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    assert abs(line["value"] - line["config"]["units_per_step"] / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    for key in ("timing", "roofline", "kernels", "cpu_baseline", "training_step", "shipped_configs", "scaling_curve_c5"):
+        assert key not in line, key  # (measured by --full only)
+    assert sorted(os.listdir(out_dir)) == ["ortho.npy"]
+    got = np.load(out_dir / "ortho.npy")
+    assert got.dtype == np.float32 and got.shape == (1, 256, 200, 200)
+    dev = torch.device("cuda:0")
+    wl = make_workload("multiviewc_200x200x1", channels=256, seed=0)
+    torch.manual_seed(0)
+    mods = [vfa_amd.VFA(256, grid_height=wl["grid_height"], cube_size=wl["cube_size"], feat_scale=1 / 8., args=wl["args"]).to(dev)
+            for _ in range(3)]
+    lats = [torch.cat([wl["features"][c][s] for c in range(wl["n_cam"])]).to(dev) for s in range(3)]
+    with torch.no_grad():
+        want = vfa_amd.aggregate_views(*mods, *lats, wl["calibs"].to(dev), wl["grid"].to(dev)).cpu().numpy()
+    assert np.abs(want).max() > 0
+    np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-6 * np.abs(want).max())

@@ -44,7 +44,27 @@ def test_vfanet_builds_with_the_reference_default_arguments(tmp_path, monkeypatc
     assert not torch.all(net2.base.layer2[0].conv1.weight == 0.5)
 
 
-def test_reference_named_alias_package_resolves_to_the_build():
+def _reference_shaped_checkout(root):
+    """A stand-in for the reference checkout behind compat/: the package layout the alias package extends (vfa/model/loss.py,
+    vfa/evaluation/pyeval/IoU.py -> cuda_op/cuda_ext.py -> ``import sort_vertices``), each module a line or two written here."""
+    files = {
+        "vfa/__init__.py": "",
+        "vfa/model/__init__.py": "",
+        "vfa/model/loss.py": "ORIGIN = 'checkout'\n",
+        "vfa/evaluation/__init__.py": "",
+        "vfa/evaluation/pyeval/__init__.py": "",
+        "vfa/evaluation/pyeval/cuda_op/__init__.py": "",
+        "vfa/evaluation/pyeval/cuda_op/cuda_ext.py": "import sort_vertices\n\nbound = sort_vertices.sort_vertices_forward\n",
+        "vfa/evaluation/pyeval/IoU.py": "from .cuda_op.cuda_ext import bound\n",
+    }
+    for rel, text in files.items():
+        path = root / rel
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(text)
+    return str(root)
+
+
+def test_reference_named_alias_package_resolves_to_the_build(tmp_path):
     """`from vfa.model.vfanet import VFANet` (reference train.py / evaluate.py) with compat/ in front of the path."""
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(REPO, "compat"), REPO]))
     env.pop("VFA_REFERENCE_ROOT", None)
@@ -53,18 +73,24 @@ def test_reference_named_alias_package_resolves_to_the_build():
             "assert a.EPSILON == 1e-6 and a.MAXIMUM_AREA_RATIO == 0.3; print('ok')")
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd="/")
     assert out.returncode == 0 and out.stdout.strip() == "ok", out.stderr
-    if os.path.isdir("/root/reference/vfa"):  # build container only: the REST of vfa.* is still the reference's
-        env["PYTHONPATH"] += os.pathsep + "/root/reference"
-        code = ("import vfa.model.loss as l, vfa.model.vfa_op as a, vfa_amd, os;"
-                "assert l.__file__.startswith('/root/reference') and a.VFA is vfa_amd.VFA; print('ok')")
-        out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd="/")
-        assert out.returncode == 0 and out.stdout.strip() == "ok", out.stderr
-        # the reference's IoU module binds its CUDA-only op to the HIP one through compat/sort_vertices.py, unedited
-        code = ("import vfa.evaluation.pyeval.IoU as i, vfa_amd.eval_ops as e;"
-                "assert i.__file__.startswith('/root/reference') and i.sort_v.__self__.__name__ == 'SortVertices';"
-                "import sort_vertices as s; assert s.sort_vertices_forward is e.sort_vertices; print('ok')")
-        out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd="/")
-        assert out.returncode == 0 and out.stdout.strip() == "ok", out.stderr
+    # with a checkout of the reference's layout behind it on the path, the REST of vfa.* resolves to that checkout
+    checkout = _reference_shaped_checkout(tmp_path / "checkout")
+    env["PYTHONPATH"] += os.pathsep + checkout
+    code = (f"import vfa.model.loss as l, vfa.model.vfa_op as a, vfa_amd, os; checkout = {checkout!r};"
+            "assert l.__file__.startswith(checkout) and l.ORIGIN == 'checkout' and a.VFA is vfa_amd.VFA; print('ok')")
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd="/")
+    assert out.returncode == 0 and out.stdout.strip() == "ok", out.stderr
+    # the checkout's IoU module binds its CUDA-only extension import to the HIP op through compat/sort_vertices.py, unedited
+    code = (f"import vfa.evaluation.pyeval.IoU as i, vfa_amd.eval_ops as e; checkout = {checkout!r};"
+            "assert i.__file__.startswith(checkout) and i.bound is e.sort_vertices;"
+            "import sort_vertices as s; assert s.sort_vertices_forward is e.sort_vertices; print('ok')")
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd="/")
+    assert out.returncode == 0 and out.stdout.strip() == "ok", out.stderr
+    # ... and the same checkout found through VFA_REFERENCE_ROOT instead of the path
+    env["PYTHONPATH"] = os.pathsep.join([os.path.join(REPO, "compat"), REPO])
+    env["VFA_REFERENCE_ROOT"] = checkout
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd="/")
+    assert out.returncode == 0 and out.stdout.strip() == "ok", out.stderr
 
 
 def test_extension_module_alias_exports_the_reference_entry_point():
