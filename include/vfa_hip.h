@@ -421,6 +421,39 @@ int vfa_pipe_collapse_relu_sum_f32(const float *const *integrals, const unsigned
 int vfa_pipe_balance_f32(int n_views, int L, int W, int n_layers, int n_scales, int reserved_cus, int mode, void *workspace,
                          size_t workspace_bytes, void *stream);
 
+/* ---- batched frames of a static rig: B frames in ONE pipelined launch (vfa_pipe.hip) ------------------------------------------------
+ *
+ * The geometry of a frame depends on the calibrations, the grid, the z-layers and the feature-map sizes only, so on a static rig it is
+ * the same for every frame of a batch.  vfa_pipe_batch_records_f32 writes the box records and tap-window headers ONCE (the same bytes
+ * vfa_pipe_boxes_f32 writes for one frame) and makes the work cuts over n_frames x n_tiles VIRTUAL tiles, frame-minor: t' = t * n_frames
+ * + b, so consecutive tiles of a run share their records and tap-window geometry.  n_views <= 32 stays a per-frame limit (the view
+ * masks are 32 bits); n_frames * n_views may exceed it.  It also leaves a batch record (frame count, run length, block count) that the
+ * frame kernel takes its run length from.
+ *
+ * vfa_pipe_batch_collapse_relu_sum_f32: integrals[k] (n_frames * n_views, Hf+2, Wf+2, 256), frame-major (what vfa_integral_images_f32
+ * makes of a stacked lateral batch); feat_absmax[k]: NULL or the statistics of that stacked batch; out (n_frames, L * W, 256).  Frame b
+ * keeps its own arithmetic: the fp16 operand split of frame b uses the power of two a single-frame call on frame b would (its own
+ * statistics; it rides on the sliver shift of its sub-tiles), so its products use the same pieces; only the association of the
+ * cross-workgroup and view / scale sums may differ from vfa_pipe_collapse_relu_sum_f32 on that frame alone.  VFA_FLAG_DUMP_VOX: one
+ * view, one scale, one layer; out receives every frame's voxel features.  A terms mismatch, like a workspace whose batch record is
+ * not this batch's, gives a map of NaNs.
+ *
+ * The batched workspace is caller-owned and EXACTLY vfa_pipe_batch_workspace_bytes(n_frames, ...) bytes: every batched call refuses
+ * another size (VFA_ERR_BAD_ARGUMENT), so a workspace made for one frame count cannot be launched with another.  Layout: offsets
+ * [0, 22) as vfa_pipe_workspace_layout, offsets[22] the batch record, offsets[23] the per-frame split exponents (25 entries);
+ * tiles[5] = the virtual tile count (6 entries).  vfa_pipe_batch_balance_f32: vfa_pipe_balance_f32 for a batched workspace. */
+size_t vfa_pipe_batch_workspace_bytes(int n_frames, int n_views, int L, int W, int n_layers, int n_scales);
+int vfa_pipe_batch_workspace_layout(int n_frames, int n_views, int L, int W, int n_layers, int n_scales, size_t *offsets, int *tiles);
+int vfa_pipe_batch_records_f32(const float *calibs, const float *grid, const float *z_layers, int n_layers, const float *corner_off,
+                               int n_views, int L, int W, int conv_kind, float img_w, float img_h, float cmin, float cmax, int n_scales,
+                               const int *feat_hw, const float *const *weights, int n_frames, int flags, void *workspace,
+                               size_t workspace_bytes, void *stream);
+int vfa_pipe_batch_collapse_relu_sum_f32(const float *const *integrals, const unsigned *const *feat_absmax, const float *const *biases,
+                                         void *workspace, size_t workspace_bytes, float *out, int n_frames, int n_views, int L, int W,
+                                         int n_layers, int n_scales, const int *feat_hw, int accumulate, int flags, void *stream);
+int vfa_pipe_batch_balance_f32(int n_frames, int n_views, int L, int W, int n_layers, int n_scales, int reserved_cus, int mode,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
 /* The weight gradient of `collapse` (training):  g_w (256, K) (+)= g_lin^T . vox  with g_lin (rows, 256) the
  * masked output gradient (vfa_relu_mask_backward_f32 / vfa_collapse_gemm_relu_backward_f32) and vox (rows, K) the voxel features of
  * the same rows, K = n_layers * 256 in the column order of the weight passed to the forward.  Six bf16 MFMA products of a three-piece
@@ -451,6 +484,8 @@ int vfa_grad_input_f32(const float *g_lin, const float *w, float *g_vox, long lo
  *                                                            replaces vfa/data/encoder.py:230-232 + the sigmoid of :238 / :278 */
 int vfa_sort_vertices_f32(const float *vertices, const uint8_t *mask, const int *num_valid, int *idx, int b, int n, int m, void *stream);
 int vfa_bev_nms_f32(const float *heatmap, float *conf, int L, int W, void *stream);
+/* vfa_bev_nms_batch_f32: the same for B maps (B, L, W) in one launch; the 5 x 5 window never crosses from one frame into the next. */
+int vfa_bev_nms_batch_f32(const float *heatmap, float *conf, int B, int L, int W, void *stream);
 
 #ifdef __cplusplus
 }

@@ -94,6 +94,14 @@ SIGNATURES = {
     "vfa_pipe_collapse_relu_sum_f32": [_vp, _vp, _vp, _vp, _c_size_t, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _c_int,
                                        _vp],
     "vfa_pipe_balance_f32": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_size_t, _vp],
+    "vfa_pipe_batch_workspace_bytes": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int],
+    "vfa_pipe_batch_workspace_layout": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp],
+    "vfa_pipe_batch_records_f32": [_vp, _vp, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_float,
+                                   _c_int, _vp, _vp, _c_int, _c_int, _vp, _c_size_t, _vp],
+    "vfa_pipe_batch_collapse_relu_sum_f32": [_vp, _vp, _vp, _vp, _c_size_t, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp,
+                                             _c_int, _c_int, _vp],
+    "vfa_pipe_batch_balance_f32": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_size_t, _vp],
+    "vfa_bev_nms_batch_f32": [_vp, _vp, _c_int, _c_int, _c_int, _vp],
 }
 
 _lib = None

@@ -213,8 +213,35 @@ class PendingOrtho:
         return self._ortho.view(1, length, width, c).permute(0, 3, 1, 2)
 
 
+def _aggregate_frames(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange, reduce_group, distributed, integrals, halo, B):
+    length, width = grid.shape[-3], grid.shape[-2]
+    c_out = vfa8.collapse.out_features
+    mods3 = [vfa8, vfa16, vfa32]
+    maps = integrals if integrals is not None else (lat8, lat16, lat32)
+    if calibs.dim() not in (3, 4) or (calibs.dim() == 4 and calibs.shape[0] != B):
+        raise ValueError(f"aggregate_views(frames={B}): calibs must be (n,3,4) or ({B},n,3,4), got {tuple(calibs.shape)}")
+    n = calibs.shape[-3]
+    if B < 0 or any(m is None or m.shape[0] != B * n for m in maps):
+        raise ValueError(f"aggregate_views(frames={B}): every scale needs {B} x {n} maps, frame-major")
+    if B == 0:
+        return torch.zeros((0, c_out, length, width), dtype=torch.float32, device=grid.device)
+    if (calibs.dim() == 3 and not distributed and n > 0
+            and vfa_op.pipe_frames_ok(mods3, n, () if integrals is not None else (lat8, lat16, lat32))):
+        ortho = vfa_op.pipe_frames(mods3, None if integrals is not None else [lat8, lat16, lat32], calibs, grid, B, crange,
+                                   integrals=integrals)
+        return ortho.view(B, length, width, c_out).permute(0, 3, 1, 2)
+    outs = []
+    for b in range(B):
+        part = slice(b * n, (b + 1) * n)
+        one = [None if m is None else m[part] for m in ((lat8, lat16, lat32) if integrals is None else (None, None, None))]
+        outs.append(aggregate_views(vfa8, vfa16, vfa32, *one, calibs[b] if calibs.dim() == 4 else calibs, grid, crange,
+                                    reduce_group=reduce_group, distributed=distributed, halo=halo,
+                                    integrals=None if integrals is None else [i[part] for i in integrals]))
+    return torch.cat(outs, 0)
+
+
 def aggregate_views(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange=(-1, 0.95), reduce_group=None,
-                    distributed=False, integrals=None, halo=None):
+                    distributed=False, integrals=None, halo=None, frames=None):
     """The camera loop of ``VFANet.forward`` for the cameras held by this process.
 
     lat* (n,C,h,w) lateral maps of the local cameras, calibs (n,3,4), grid (1,L,W,3)
@@ -227,7 +254,13 @@ def aggregate_views(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange
     call returns ``(band (1,C,rows,W), (row0, row1), (top, bottom))``.
     ``integrals``: the three integral-image batches instead of the lateral maps (producer fusion, inference on the fused frame
     path only; ``lat*`` may then be None).
+    ``frames=B``: a batch of B frames -> (B,C,L,W).  lat* (or ``integrals``) hold B*n maps, frame-major; calibs is ONE rig (n,3,4)
+    for every frame, or (B,n,3,4) a rig per frame.  One rig and inference: ONE launch of the pipelined kernel for the whole batch
+    (``vfa_op.pipe_frames``); anything else -- a rig per frame, gradients, distributed reductions -- runs frame by frame and stacks.
     """
+    if frames is not None:
+        return _aggregate_frames(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange, reduce_group, distributed, integrals,
+                                 halo, int(frames))
     length, width = grid.shape[-3], grid.shape[-2]
     n = calibs.shape[0]
     # a per-call flag of the MFMA entry points (include/vfa_hip.h: VFA_FLAG_RESERVED_CUS), no library state

@@ -90,8 +90,12 @@ __global__ __launch_bounds__(256) void sort_vertices_kernel(const float *__restr
 }
 
 // conf[l, w] = s if s == max over the 5 x 5 neighbourhood (padding 2, -inf outside) else 0, s = 1 / (1 + exp(-heatmap[l, w]))
+// Batched (vfa_bev_nms_batch_f32): frame blockIdx.z, its own (L, W) map -- the window stops at the frame's edges like the padding of
+// one map, so a peak of frame b + 1 never suppresses one of frame b
 __global__ __launch_bounds__(256) void bev_nms_kernel(const float *__restrict__ heat, float *__restrict__ conf, int L, int W)
 {
+    heat += (size_t)blockIdx.z * L * W;
+    conf += (size_t)blockIdx.z * L * W;
     const int w = blockIdx.x * 32 + (threadIdx.x & 31), l = blockIdx.y * 8 + (threadIdx.x >> 5);
     if (l >= L || w >= W) return;
     auto sig = [](float x) { return 1.0f / (1.0f + expf(-x)); };
@@ -125,6 +129,15 @@ int vfa_bev_nms_f32(const float *heatmap, float *conf, int L, int W, void *strea
     if (L < 0 || W < 0) return VFA_ERR_BAD_ARGUMENT;
     if (L == 0 || W == 0) return 0;
     hipLaunchKernelGGL(bev_nms_kernel, dim3((W + 31) / 32, (L + 7) / 8), dim3(256), 0, (hipStream_t)stream, heatmap, conf, L, W);
+    return (int)hipGetLastError();
+}
+
+int vfa_bev_nms_batch_f32(const float *heatmap, float *conf, int B, int L, int W, void *stream)
+{
+    if (B < 0 || L < 0 || W < 0) return VFA_ERR_BAD_ARGUMENT;
+    if (B == 0 || L == 0 || W == 0) return 0;
+    if (B > 65535) return VFA_ERR_UNSUPPORTED; // (grid z)
+    hipLaunchKernelGGL(bev_nms_kernel, dim3((W + 31) / 32, (L + 7) / 8, B), dim3(256), 0, (hipStream_t)stream, heatmap, conf, L, W);
     return (int)hipGetLastError();
 }
 

@@ -86,6 +86,13 @@ constexpr int kChunks = 8192, kMaxBlocks = 512;
 //   u64 cycles[kMaxBlocks]       at byte 4096: cycles every workgroup of the LAST launch took
 constexpr int kBalTag = kMaxBlocks + 1, kBalSig = kMaxBlocks + 2, kBalCyclesAt = 4096, kBalanceBytes = kBalCyclesAt + kMaxBlocks * 8;
 constexpr int kSigAt = kChunks + 1; // the cuts kernel leaves the frame's total cost behind the last entry of chunk_start (2 ints)
+// Batch record of a batched workspace (vfa_pipe_batch_records_f32 writes it, the batched frame kernel reads it): the launch takes its
+// run length from here -- the one the cuts were made for -- and refuses (a map of NaNs) a workspace made for another frame count
+constexpr int kMetaTag = 0, kMetaFrames = 1, kMetaRt = 2, kMetaBlocks = 3, kMetaTiles = 4, kMetaInts = 8;
+constexpr int kMetaMagic = 0x56464142;
+// batched frames: binary places by which the fp16 split of one frame may lie below the launch's (pipe_frame_exp_kernel); with the
+// largest sliver shift (48) the sub-tile's factor 2^-(shift + dea) stays a normal fp32 power of two
+constexpr int kMaxFrameDea = 126 - 48;
 constexpr int kVis = 1;
 constexpr int kTileLive = 1, kTileDirect = 2;
 // VFA_FLAG_DUMP_VOX (diagnostic build): with ONE view, ONE scale and ONE layer `out` receives the pooled fp32 voxel features (cell,
@@ -319,7 +326,8 @@ struct CutArgs {
     unsigned long long *chunk_cost; // (kChunks + 1): estimated cost of everything in front of the group boundary a piece starts at
     SplitArgs split;                // wmax_count > 0: the blocks behind block 0 leave the partial maxima of |W| (they need nothing of the frame)
     long long wmax_count;           // weights per scale
-    int staged;                     // 1: the launch has LDS for the masks and sub-tile costs of the whole frame (n_scales * n_tiles * (1 + n_views) words)
+    int staged;                     // 1: the launch has LDS for the masks and sub-tile costs of the whole frame (n_scales * geo_tiles * (1 + n_views) words)
+    int nf, geo_tiles;              // batched (BATCH): n_tiles = nf * geo_tiles virtual tiles t' = t * nf + b read the tables of tile t
 };
 #ifdef VFA_CUTS_STAMPS
 __device__ unsigned long long g_cut_stamps[16];
@@ -327,6 +335,7 @@ __device__ unsigned long long g_cut_stamps[16];
 #else
 #define CUT_STAMP(i) do { } while (0)
 #endif
+template <bool BATCH = false>
 __global__ __launch_bounds__(1024) void pipe_cuts_kernel(CutArgs a)
 {
     __shared__ unsigned long long part[1024];
@@ -355,13 +364,15 @@ __global__ __launch_bounds__(1024) void pipe_cuts_kernel(CutArgs a)
     // round trips per run of four tiles -- 105 us for the Wildtrack frame, 54 for MultiviewX, 29 for 156 x 156 x 5 (round 6, when the
     // sub-tile costs arrived; the masks alone: 18).  Frames whose tables do not fit (512 x 512 x 32: 221 KB per band) walk global memory.
     extern __shared__ unsigned cut_stage[]; // [scale][tile] masks, then [scale][tile][view] costs
-    const size_t cost_base = (size_t)a.n_scales * n_tiles;
+    const int geo_tiles = BATCH ? a.geo_tiles : n_tiles;
+    auto geo_of = [&](int t) -> int { if constexpr (BATCH) return t / a.nf; else return t; };
+    const size_t cost_base = (size_t)a.n_scales * geo_tiles;
     if (a.staged) {
         for (int s2 = 0; s2 < a.n_scales; ++s2) { // (a loop per table: one flat loop with the table picked per word measured slower)
             const unsigned *lv = s2 == 0 ? a.live[0] : (s2 == 1 ? a.live[1] : a.live[2]);
             const unsigned *sc = s2 == 0 ? a.subcost[0] : (s2 == 1 ? a.subcost[1] : a.subcost[2]);
-            for (int t = tid; t < n_tiles; t += 1024) cut_stage[(size_t)s2 * n_tiles + t] = lv[t] & view_mask;
-            const int n_cost = n_tiles * a.n_views;
+            for (int t = tid; t < geo_tiles; t += 1024) cut_stage[(size_t)s2 * geo_tiles + t] = lv[t] & view_mask;
+            const int n_cost = geo_tiles * a.n_views;
             for (int i = tid; i < n_cost; i += 1024) cut_stage[cost_base + (size_t)s2 * n_cost + i] = sc[i];
         }
         __syncthreads();
@@ -371,16 +382,18 @@ __global__ __launch_bounds__(1024) void pipe_cuts_kernel(CutArgs a)
         return [&, r](int s2, int off) -> unsigned {
             const int t = r * rt + off;
             if (t >= n_tiles) return 0u;
-            if (a.staged) return cut_stage[(size_t)s2 * n_tiles + t];
+            const int g = geo_of(t);
+            if (a.staged) return cut_stage[(size_t)s2 * geo_tiles + g];
             const unsigned *lv = s2 == 0 ? a.live[0] : (s2 == 1 ? a.live[1] : a.live[2]);
-            return lv[t] & view_mask;
+            return lv[g] & view_mask;
         };
     };
     auto cost_of = [&](int r) {
         return [&, r](int s2, int off, int v) -> unsigned {
-            if (a.staged) return cut_stage[cost_base + ((size_t)s2 * n_tiles + (r * rt + off)) * a.n_views + v];
+            const int g = geo_of(r * rt + off);
+            if (a.staged) return cut_stage[cost_base + ((size_t)s2 * geo_tiles + g) * a.n_views + v];
             const unsigned *sc = s2 == 0 ? a.subcost[0] : (s2 == 1 ? a.subcost[1] : a.subcost[2]);
-            return sc[(size_t)(r * rt + off) * a.n_views + v];
+            return sc[(size_t)g * a.n_views + v];
         };
     };
     // entries = (run, scale) in the kernel's order; a thread takes a contiguous range of them
@@ -490,6 +503,10 @@ struct PipeArgs {
     int debug;
     int *balance;                   // balance state of the workspace (kBalanceBytes: see kBalTag)
     const int *wexp;                // (kMaxScales) scale exponent of the split collapse weight (fp16 form); [kMaxScales]: 2 = fp16 fragments, 3 = bf16
+    // batched frames (pipe_kernel<.., BATCH>, vfa_pipe_batch_*): tile index = virtual tile t' = t * nf + b (frame-minor)
+    int nf;                         // frames of the launch (1 for the single-frame entry points)
+    const unsigned *fdea;           // (kMaxScales, nf) binary places frame b's fp16 split lies below the launch's (pipe_frame_exp_kernel)
+    const int *meta;                // batch record of the workspace (kMetaInts: see kMetaTag), written by the batched geometry call
 };
 
 struct DevMasks {
@@ -624,9 +641,14 @@ __device__ __forceinline__ void read_frags3(unsigned pa, bf16x8 &p0, bf16x8 &p1,
 // parameter, not a branch on a.rt: the contribution code of the longer runs in the same loop body cost the step loop 3-5 %.
 // RTC: the run length as a compile-time fact (2 or 4; 0 = read from the arguments): the generator's loops over the tiles of a run
 // unroll and its state stays out of the pooling loops' registers (the tile-by-tile templates gained 2 % from the same).
-template <int TERMS, bool DIAG, bool SMALL = false, bool RT1 = false, int RTC = 0>
+// BATCH: a.nf frames of one static rig in ONE launch (vfa_pipe_batch_collapse_relu_sum_f32).  The work is laid out over nf * n_tiles
+// VIRTUAL tiles t' = t * nf + b: everything geometric (masks, sliver shifts, headers, records, cells) is read with tile t = t' / nf,
+// the frame b selects only the integral images (b * n_views + view) and the map (b * L * W).  The run length comes from the
+// workspace (the geometry call made the cuts for it), not from the arguments.
+template <int TERMS, bool DIAG, bool SMALL = false, bool RT1 = false, int RTC = 0, bool BATCH = false>
 __global__ __launch_bounds__(threads_of(TERMS)) void pipe_kernel(PipeArgs a)
 {
+    static_assert(!BATCH || (!SMALL && !RT1), "batched frames: the generic eight-step templates only");
     static_assert(!SMALL || TERMS != 6, "the four-step phase exists in the sixteen-wave layout only");
     static_assert(!RT1 || (TERMS != 6 && !SMALL), "RT1: the sixteen-wave layout's eight-step phase");
     constexpr int kPS = SMALL ? 4 : 8, kPSh = SMALL ? 2 : 3; // steps of a phase; step i: phase i >> kPSh, position i & (kPS - 1)
@@ -657,8 +679,10 @@ __global__ __launch_bounds__(threads_of(TERMS)) void pipe_kernel(PipeArgs a)
     const int nblk = gridDim.x;
     // The weight fragments in the workspace were split for ONE arithmetic (the geometry call's flags); a launch that asks for the other
     // would read fp16 pieces as bf16 ones: fail loudly -- a map of NaNs -- instead of returning plausible garbage.
-    if (uniform_i(a.wexp[kMaxScales]) != (F16 ? 2 : 3)) {
-        for (size_t i = (size_t)blockIdx.x * blockDim.x + tid; i < (size_t)a.L * a.W * kC; i += (size_t)nblk * blockDim.x)
+    // (batched: the same for a workspace whose geometry was made for another batch)
+    if (uniform_i(a.wexp[kMaxScales]) != (F16 ? 2 : 3) ||
+        (BATCH && (uniform_i(a.meta[kMetaTag]) != kMetaMagic || uniform_i(a.meta[kMetaFrames]) != a.nf))) {
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + tid; i < (size_t)a.L * a.W * kC * (BATCH ? a.nf : 1); i += (size_t)nblk * blockDim.x)
             a.out[i] = __uint_as_float(0x7fc00000u);
         return;
     }
@@ -674,7 +698,7 @@ __global__ __launch_bounds__(threads_of(TERMS)) void pipe_kernel(PipeArgs a)
         tb = uniform_i(a.chunk_start[c0]); kb = uniform_i(a.chunk_rank[c0]);
         te = uniform_i(a.chunk_start[c1]); ke = uniform_i(a.chunk_rank[c1]);
     };
-    const int rt = (RT1 || SMALL) ? 1 : (RTC ? RTC : a.rt); // tiles of a run: 1, 2 or 4 (a compile-time 1 in the tile-by-tile templates: their generator folds to one tile)
+    const int rt = (RT1 || SMALL) ? 1 : (RTC ? RTC : (BATCH ? uniform_i(a.meta[kMetaRt]) : a.rt)); // tiles of a run: 1, 2 or 4 (a compile-time 1 in the tile-by-tile templates: their generator folds to one tile)
     int r_begin, k_begin, r_end, k_end; // runs of rt tiles, groups of a run (vfa_pipe_seq.h)
     range_of(lb, r_begin, k_begin, r_end, k_end);
     unsigned long long *wg_cycles = reinterpret_cast<unsigned long long *>(reinterpret_cast<unsigned char *>(a.balance) + kBalCyclesAt) + lb;
@@ -686,6 +710,9 @@ __global__ __launch_bounds__(threads_of(TERMS)) void pipe_kernel(PipeArgs a)
     DevMasks masks;
     masks.l0 = a.sc[0].live; masks.l1 = a.sc[1].live; masks.l2 = a.sc[2].live;
     masks.view_mask = view_mask;
+    // virtual tile -> (tile of the rig's geometry, frame); the identity for one frame
+    auto geo_of = [&](int t) -> int { if constexpr (BATCH) return t / a.nf; else return t; };
+    auto frame_of = [&](int t) -> int { if constexpr (BATCH) return t - (t / a.nf) * a.nf; else return 0; };
 
     // a run is SHARED when another workgroup holds groups of it too
     auto shared_run = [&](int run) { return (run == r_begin && k_begin > 0) || (run == r_end && k_end > 0); };
@@ -810,14 +837,16 @@ __global__ __launch_bounds__(threads_of(TERMS)) void pipe_kernel(PipeArgs a)
         // output rows of a tile: register i of lane (r, h) is row (i & 3) + 8 (i >> 2) + 4 h of the 32 x 32 block, column r
         auto write_tile = [&](int tile, const f32x16 &v, bool have) __attribute__((always_inline)) {
             if (DIAG && (a.debug & kDbgDumpVox)) return; // (the output buffer holds the dumped voxel features)
-            const int tl = tile / a.tiles_w, tw = tile - tl * a.tiles_w;
+            const int gt = geo_of(tile);
+            const int tl = gt / a.tiles_w, tw = gt - tl * a.tiles_w;
             float extra = 0.0f; // fully masked (view, scale) of this tile: vox = 0 -> relu(bias)
 #pragma unroll
             for (int s = 0; s < kMaxScales; ++s)
-                if (s < a.n_scales) extra += (float)(a.n_views - __popc(masks(s, tile))) * (F16 ? relu_t(bc[s]) * inv_of(s) : relu_t(bc[s]));
+                if (s < a.n_scales) extra += (float)(a.n_views - __popc(masks(s, gt))) * (F16 ? relu_t(bc[s]) * inv_of(s) : relu_t(bc[s]));
             int h2 = h, r2 = r;
             asm volatile("" : "+v"(h2), "+v"(r2)); // (keeps the 16 row offsets out of long-lived registers)
             float *ocol = a.out + wave * 32 + r2;
+            if constexpr (BATCH) ocol += (size_t)frame_of(tile) * a.L * a.W * kC;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int row = (i & 3) + 8 * (i >> 2) + 4 * h2;
@@ -879,7 +908,7 @@ __global__ __launch_bounds__(threads_of(TERMS)) void pipe_kernel(PipeArgs a)
             // live-view mask of (scale s2, tile `off` of the lane's run): vector loads (L2 hits: the geometry pass wrote them)
             auto mask_of = [&](int s2, int off) -> unsigned {
                 const unsigned *lv = s2 == 0 ? a.sc[0].live : (s2 == 1 ? a.sc[1].live : a.sc[2].live);
-                return (on && base_tile + off < a.n_tiles) ? (lv[base_tile + off] & view_mask) : 0u;
+                return (on && base_tile + off < a.n_tiles) ? (lv[geo_of(base_tile + off)] & view_mask) : 0u;
             };
             int gt = 0; // groups of the run: per scale, its live sub-tiles in fours
 #pragma unroll 1
@@ -909,7 +938,13 @@ __global__ __launch_bounds__(threads_of(TERMS)) void pipe_kernel(PipeArgs a)
                         unsigned shifts = 0u; // (fp16 split: the sliver shift of every sub-tile's (tile, scale))
                         if constexpr (F16) {
                             const unsigned *shp = s2 == 0 ? a.sc[0].shift : (s2 == 1 ? a.sc[1].shift : a.sc[2].shift);
-                            for (int j = 0; j < nj; ++j) shifts |= (shp[base_tile + sub_tile_off(subs, j)] & 0xffu) << (8 * j);
+                            for (int j = 0; j < nj; ++j) {
+                                const int t = base_tile + sub_tile_off(subs, j);
+                                unsigned sh = shp[geo_of(t)] & 0xffu;
+                                // (batched: frame b's own power of two -- 2^(ea_b - shift) = 2^(ea - (shift + dea_b)), ea the launch's)
+                                if constexpr (BATCH) sh += a.fdea[s2 * a.nf + frame_of(t)];
+                                shifts |= sh << (8 * j);
+                            }
                         }
                         const unsigned w = (unsigned)s2 | ((unsigned)nj << 15) | (r + 1 < hi ? 1u << 20 : 0u) | ((unsigned)ci << 21);
                         *reinterpret_cast<uint4 *>(&s_groups[(base + r) & (kGroupRing - 1)][0]) = make_uint4((unsigned)t, subs, w, shifts);
@@ -940,7 +975,7 @@ __global__ __launch_bounds__(threads_of(TERMS)) void pipe_kernel(PipeArgs a)
             const int layer = (int)((v.z >> 2) & 1023u), nj = (int)((v.z >> 15) & 7u);
             int j = lane >> 3;
             j = j < nj ? j : nj - 1;
-            const int view = sub_view(v.y, j), tile = (int)v.x * rt + sub_tile_off(v.y, j);
+            const int view = sub_view(v.y, j), tile = geo_of((int)v.x * rt + sub_tile_off(v.y, j));
             const uint4 c1 = *reinterpret_cast<const uint4 *>(&s_phase[n & 3][8]), c2 = *reinterpret_cast<const uint4 *>(&s_phase[n & 3][12]);
             const unsigned long long item = (unsigned long long)((unsigned)tile * c2.z + (unsigned)layer * c2.w + (unsigned)view);
             const unsigned long long p = ((unsigned long long)c1.w << 32 | c1.z) + item * kHdrBytes + (unsigned)(lane & 7) * 4u;
@@ -957,7 +992,7 @@ __global__ __launch_bounds__(threads_of(TERMS)) void pipe_kernel(PipeArgs a)
             if (uniform_i((int)v.x) < 0) return;
             const int layer = (int)((v.z >> 2) & 1023u), nj = (int)((v.z >> 15) & 7u);
             const int jj = j < nj ? j : 0;
-            const int tile = (int)v.x * rt + sub_tile_off(v.y, jj);
+            const int vtile = (int)v.x * rt + sub_tile_off(v.y, jj), tile = geo_of(vtile);
             // (the header read stays BEHIND the validity branch and indexed by jj: reading slot j in front of it -- one round trip
             // less -- ended in memory faults on full-size frames in the optimised build only; not understood, not used)
             const uint2 hd = *reinterpret_cast<const uint2 *>(&s_hdr[n & 3][jj * 8]);
@@ -968,7 +1003,8 @@ __global__ __launch_bounds__(threads_of(TERMS)) void pipe_kernel(PipeArgs a)
             const unsigned ea64 = (c2.y & 0xffff0000u) - (F16 ? ((v.w >> (8 * jj)) & 0xffu) << 16 : 0u); // (the shift of the sub-tile's (tile, scale))
             const unsigned long long item = (unsigned long long)((unsigned)tile * c2.z + (unsigned)layer * c2.w + (unsigned)view);
             const unsigned long long img = ((unsigned long long)c0.y << 32 | c0.x) +
-                                           (unsigned long long)view * (unsigned)((Hf + 2) * (Wf + 2)) * kSlotBytes + (unsigned)(q * kQSlot);
+                                           (unsigned long long)(frame_of(vtile) * a.n_views + view) * (unsigned)((Hf + 2) * (Wf + 2)) * kSlotBytes +
+                                           (unsigned)(q * kQSlot);
             const unsigned long long rec = ((unsigned long long)c0.w << 32 | c0.z) + item * (kTileBoxes * kRecBytes);
             const unsigned long long wsl = ((unsigned long long)c1.y << 32 | c1.x) +
                                            (unsigned long long)(((unsigned)layer * 8u * kSteps + (unsigned)q * 4u) * (unsigned)kWPlanes * 64u) * 16u;
@@ -1373,11 +1409,11 @@ __global__ __launch_bounds__(threads_of(TERMS)) void pipe_kernel(PipeArgs a)
                 const float xs[4] = {box_quotient_scaled(v.x, bx.asc, bx.scl), box_quotient_scaled(v.y, bx.asc, bx.scl),
                                      box_quotient_scaled(v.z, bx.asc, bx.scl), box_quotient_scaled(v.w, bx.asc, bx.scl)};
                 if (DIAG && (a.debug & kDbgDumpVox)) { // (one view, one scale, one layer: every sub-tile is a tile of its own; the power-of-two factor of the fp16 split taken out again: exact)
-                    const int tl = tile / a.tiles_w, tw = tile - tl * a.tiles_w, brow = phalf * 16 + pb;
+                    const int gt = geo_of(tile), tl = gt / a.tiles_w, tw = gt - tl * a.tiles_w, brow = phalf * 16 + pb;
                     const int cl = tl * kTileL + (brow >> 3), cw = tw * kTileW + (brow & 7);
                     const float back = bx.back;
                     if (cl < a.L && cw < a.W)
-                        *reinterpret_cast<float4 *>(a.out + (size_t)(cl * a.W + cw) * kC + quarter_of(k) * 64 + (int)piece * 16 + pi * 4) =
+                        *reinterpret_cast<float4 *>(a.out + (size_t)frame_of(tile) * a.L * a.W * kC + (size_t)(cl * a.W + cw) * kC + quarter_of(k) * 64 + (int)piece * 16 + pi * 4) =
                             make_float4(xs[0] * back, xs[1] * back, xs[2] * back, xs[3] * back);
                 }
                 // x = hi + lo + r, |r| <= 2^-17 |x|: hi = RNE bf16(x), lo = RNE bf16(x - hi)
@@ -1913,6 +1949,53 @@ __global__ __launch_bounds__(kMaxBlocks) void pipe_balance_kernel(int *bal, cons
     }
 }
 
+// Batched frames, fp16 split: every frame keeps the power of two of its own single-frame call.  One workgroup per scale: ea_b of frame
+// b from ITS statistics (entries [b * stride, b * stride + count)), the launch's ea = max_b ea_b (its statistic goes to synth[scale]:
+// the frame kernel's s_amax reduction finds that exponent again), and dea[scale][b] = ea - ea_b, which the frame kernel adds to the
+// sliver shift of every sub-tile of frame b: voxel features times 2^(ea - shift - dea_b) = 2^(ea_b - shift), the bias and the way back
+// to the map's units likewise -- the same pieces, the same products as frame b alone.
+struct FrameExpArgs {
+    const unsigned *amax[kMaxScales];
+    int count[kMaxScales];
+    long long stride[kMaxScales];
+    unsigned *dea, *synth;
+    int nf;
+};
+__global__ __launch_bounds__(256) void pipe_frame_exp_kernel(FrameExpArgs a)
+{
+    __shared__ unsigned part[4];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const unsigned *base = s == 0 ? a.amax[0] : (s == 1 ? a.amax[1] : a.amax[2]);
+    const int count = s == 0 ? a.count[0] : (s == 1 ? a.count[1] : a.count[2]);
+    const long long stride = s == 0 ? a.stride[0] : (s == 1 ? a.stride[1] : a.stride[2]);
+    int ea_max = -(1 << 20);
+    unsigned m_at = 0u;
+    for (int b = 0; b < a.nf; ++b) {
+        unsigned m = 0u;
+        for (int i = tid; i < count; i += 256) m = max(m, base[b * stride + i]);
+        m = wave_max_u32(m);
+        if ((tid & 63) == 0) part[tid >> 6] = m;
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned mm = max(max(part[0], part[1]), max(part[2], part[3]));
+            const int ea = split_exponent(mm, kExpA);
+            a.dea[s * a.nf + b] = (unsigned)ea;
+            if (ea > ea_max) { ea_max = ea; m_at = mm; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        for (int b = 0; b < a.nf; ++b) a.dea[s * a.nf + b] = (unsigned)min(ea_max - (int)a.dea[s * a.nf + b], kMaxFrameDea);
+        a.synth[s] = m_at;
+    }
+}
+__global__ void pipe_meta_kernel(int *meta, int nf, int rt, int nblk, int v_tiles)
+{
+    if (threadIdx.x == 0) {
+        meta[kMetaTag] = kMetaMagic; meta[kMetaFrames] = nf; meta[kMetaRt] = rt; meta[kMetaBlocks] = nblk; meta[kMetaTiles] = v_tiles;
+    }
+}
+
 // workgroups of a launch of the frame kernel: one per CU (less the reserved ones), a multiple of eight
 inline int pipe_blocks(int n_tiles, int reserved_cus)
 {
@@ -1932,15 +2015,21 @@ inline int pipe_blocks(int n_tiles, int reserved_cus)
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct PipeLayout {
-    size_t live[kMaxScales], shifts[kMaxScales], subcost[kMaxScales], tickets, globs, masks_bytes, hdrs[kMaxScales], recs[kMaxScales], wfrag[kMaxScales], chunks, ranks, costs, partial, slots, diag, balance, wmax, wexp, amax, total;
+    size_t live[kMaxScales], shifts[kMaxScales], subcost[kMaxScales], tickets, globs, masks_bytes, hdrs[kMaxScales], recs[kMaxScales], wfrag[kMaxScales], chunks, ranks, costs, partial, slots, diag, balance, wmax, wexp, amax, meta, fdea, total;
     int tiles_l, tiles_w, n_tiles;
+    int v_tiles; // tiles of the work: n_tiles, or n_frames * n_tiles virtual tiles of a batched workspace
 };
-inline PipeLayout layout_of(int n_views, int L, int W, int nl, int n_scales)
+// n_frames = 0: the single-frame workspace of vfa_pipe_workspace_bytes; n_frames >= 1: the batched one (the geometry per tile of the
+// rig once, everything the work cuts and the frame kernel index by tile sized for the virtual tiles, the batch record and the
+// per-frame split exponents behind the rest)
+inline PipeLayout layout_of(int n_views, int L, int W, int nl, int n_scales, int n_frames = 0)
 {
     PipeLayout w;
     w.tiles_l = (L + kTileL - 1) / kTileL;
     w.tiles_w = (W + kTileW - 1) / kTileW;
     w.n_tiles = w.tiles_l * w.tiles_w;
+    const int nf = n_frames > 0 ? n_frames : 1;
+    w.v_tiles = w.n_tiles * nf;
     size_t off = 0;
     for (int s = 0; s < kMaxScales; ++s) { // view masks and tickets first, contiguous: zeroed by ONE memset
         w.live[s] = off;
@@ -1951,7 +2040,7 @@ inline PipeLayout layout_of(int n_views, int L, int W, int nl, int n_scales)
         off = align_up(off + (s < n_scales ? (size_t)w.n_tiles * 4 : 0), 256);
     }
     w.tickets = off; // (one per (run, matrix wave); sized for runs of one tile)
-    off = align_up(off + (size_t)w.n_tiles * 8 * 4, 256);
+    off = align_up(off + (size_t)w.v_tiles * 8 * 4, 256);
     w.globs = off;
     off = align_up(off + (size_t)w.n_tiles * 4, 256);
     for (int s = 0; s < kMaxScales; ++s) { // (zeroed with the masks: the geometry pass adds the sub-tiles' costs up)
@@ -1970,12 +2059,17 @@ inline PipeLayout layout_of(int n_views, int L, int W, int nl, int n_scales)
     w.ranks = off;   off = align_up(off + (kChunks + 1) * sizeof(int), 256);
     w.costs = off;   off = align_up(off + (kChunks + 1) * sizeof(unsigned long long), 256);
     w.partial = off; off = align_up(off + (size_t)kMaxBlocks * 2 * kRunTiles * 8 * 16 * 64 * sizeof(float), 256); // hand-off parts of the (first, last) run of a workgroup
-    w.slots = off;   off = align_up(off + (size_t)pipe_blocks(w.n_tiles, 0) * kRunTiles * kMaxScales * contributions_of(n_views) * 8 * 16 * 64 * sizeof(float), 256); // contributions to the tiles of the run a workgroup is in
+    w.slots = off;   off = align_up(off + (size_t)pipe_blocks(w.v_tiles, 0) * kRunTiles * kMaxScales * contributions_of(n_views) * 8 * 16 * 64 * sizeof(float), 256); // contributions to the tiles of the run a workgroup is in
     w.diag = off;    off = align_up(off + (size_t)kMaxBlocks * 8 * sizeof(unsigned long long), 256);
     w.balance = off; off = align_up(off + kBalanceBytes, 256); // work-cut bounds per workgroup + the last launch's times (vfa_pipe_balance_f32)
     w.wmax = off;    off = align_up(off + (size_t)kMaxScales * kWmaxParts * sizeof(unsigned), 256); // fp16 split: partial maxima of |W| per scale,
     w.wexp = off;    off = align_up(off + (kMaxScales + 1) * sizeof(int), 256);                            // ... the weight exponents,
-    w.amax = off;    off = align_up(off + (size_t)kMaxScales * kFallbackStats * sizeof(unsigned), 256); // ... feature statistics made here for callers that pass none
+    w.amax = off;    off = align_up(off + (size_t)nf * kMaxScales * kFallbackStats * sizeof(unsigned), 256); // ... feature statistics made here for callers that pass none
+    w.meta = w.fdea = off;
+    if (n_frames > 0) {
+        w.meta = off; off = align_up(off + kMetaInts * sizeof(int), 256);
+        w.fdea = off; off = align_up(off + (size_t)kMaxScales * (nf + 1) * sizeof(unsigned), 256); // (kMaxScales, nf) + the launch's statistic per scale
+    }
     w.total = off;
     return w;
 }
@@ -1993,6 +2087,257 @@ inline int frame_run_tiles(int n_views, int n_tiles, int n_scales, int nl)
 inline bool dims_ok(int n_views, int L, int W, int nl, int n_scales)
 {
     return n_views >= 0 && L >= 0 && W >= 0 && nl >= 1 && n_scales >= 1 && n_scales <= kMaxScales;
+}
+
+// the geometry of a frame (or of the rig of a batch: the same records) into the workspace laid out as `lay`
+int boxes_impl(const float *calibs, const float *grid, const float *z_layers, int n_layers, const float *corner_off, int n_views, int L, int W,
+               int conv_kind, float img_w, float img_h, float cmin, float cmax, int n_scales, const int *feat_hw, int flags, void *workspace,
+               size_t workspace_bytes, void *stream, int n_frames)
+{
+    const int terms = flags & VFA_FLAG_TERMS_MASK;
+    if ((flags & ~VFA_FLAG_TERMS_MASK) || (terms != 0 && terms != 2 && terms != 3 && terms != 4 && terms != 6)) return VFA_ERR_BAD_ARGUMENT;
+    if (!dims_ok(n_views, L, W, n_layers, n_scales) || conv_kind < 0 || conv_kind > 2 || !feat_hw) return VFA_ERR_BAD_ARGUMENT;
+    if (n_views > 32) return VFA_ERR_UNSUPPORTED; // live-view masks are 32 bits wide
+    const PipeLayout lay = layout_of(n_views, L, W, n_layers, n_scales, n_frames);
+    if (lay.n_tiles == 0 || n_views == 0) return 0;
+    if ((long long)n_views * lay.n_tiles >= (1ll << 31) - 2) return VFA_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < lay.total || (n_frames > 0 && workspace_bytes != lay.total)) return VFA_ERR_BAD_ARGUMENT;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
+    RecordArgs a;
+    a.g = BoxGeom{calibs, grid, z_layers, corner_off, conv_kind, img_w, img_h, cmin, cmax};
+    a.n_views = n_views; a.L = L; a.W = W; a.tiles_w = lay.tiles_w; a.n_tiles = lay.n_tiles; a.n_scales = n_scales; a.nl = n_layers;
+    a.win_slots = terms == 6 ? kWinSlots3 : kWinSlots; // (the kernel variant that will read these records)
+    for (int k = 0; k < kMaxScales; ++k) {
+        a.dims[k].Hf = k < n_scales ? feat_hw[2 * k] : 1;
+        a.dims[k].Wf = k < n_scales ? feat_hw[2 * k + 1] : 1;
+        if (a.dims[k].Hf <= 0 || a.dims[k].Wf <= 0 || a.dims[k].Hf > 65533 || a.dims[k].Wf > 65533) return VFA_ERR_BAD_ARGUMENT;
+        // (tap positions of a direct item are byte offsets into one view's padded image, 32 bits)
+        if ((unsigned long long)(a.dims[k].Hf + 2) * (a.dims[k].Wf + 2) * kSlotBytes >= (1ull << 32)) return VFA_ERR_UNSUPPORTED;
+        a.live[k] = reinterpret_cast<unsigned *>(ws + lay.live[k]);
+        a.shift[k] = reinterpret_cast<unsigned *>(ws + lay.shifts[k]);
+        a.subcost[k] = reinterpret_cast<unsigned *>(ws + lay.subcost[k]);
+        a.hdrs[k] = ws + lay.hdrs[k];
+        a.recs[k] = ws + lay.recs[k];
+    }
+    a.globs = reinterpret_cast<unsigned *>(ws + lay.globs);
+    const hipError_t e = zero_fill(ws, lay.masks_bytes, s); // view masks, tile tickets, counters (a kernel, not hipMemsetAsync: see vfa_geom.h)
+    if (e != hipSuccess) return (int)e;
+    const long long units = (long long)n_views * lay.n_tiles * n_layers; // (view, tile, layer)
+    if ((units + 1) / 2 >= (1ll << 31)) return VFA_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(pipe_records_kernel, dim3((unsigned)((units + 1) / 2)), dim3(kWave), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+// work cuts + split weights; n_frames > 0: over the virtual tiles of a batched workspace, the run length `rt` (the batch record keeps it)
+int cuts_impl(int n_views, int L, int W, int n_layers, int n_scales, const float *const *weights, int flags, void *workspace,
+              size_t workspace_bytes, void *stream, int n_frames, int *rt_out)
+{
+    const int terms = flags & VFA_FLAG_TERMS_MASK;
+    if ((flags & ~VFA_FLAG_TERMS_MASK) || (terms != 0 && terms != 2 && terms != 3 && terms != 4 && terms != 6)) return VFA_ERR_BAD_ARGUMENT;
+    if (!dims_ok(n_views, L, W, n_layers, n_scales)) return VFA_ERR_BAD_ARGUMENT;
+    if (n_views > 32) return VFA_ERR_UNSUPPORTED;
+    const PipeLayout lay = layout_of(n_views, L, W, n_layers, n_scales, n_frames);
+    if (lay.n_tiles == 0 || n_views == 0) return 0;
+    if (!workspace || workspace_bytes < lay.total || (n_frames > 0 && workspace_bytes != lay.total)) return VFA_ERR_BAD_ARGUMENT;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
+    CutArgs ca;
+    for (int k = 0; k < kMaxScales; ++k) ca.live[k] = reinterpret_cast<const unsigned *>(ws + lay.live[k < n_scales ? k : 0]);
+    ca.globs = reinterpret_cast<const unsigned *>(ws + lay.globs);
+    for (int k = 0; k < kMaxScales; ++k) ca.subcost[k] = reinterpret_cast<const unsigned *>(ws + lay.subcost[k < n_scales ? k : 0]);
+    ca.n_scales = n_scales; ca.n_tiles = lay.v_tiles; ca.n_views = n_views; ca.nl = n_layers;
+    ca.nf = n_frames > 0 ? n_frames : 1; ca.geo_tiles = lay.n_tiles;
+    ca.rt = frame_run_tiles(n_views, lay.v_tiles, n_scales, n_layers);
+    if (rt_out) *rt_out = ca.rt;
+    ca.chunk_start = reinterpret_cast<int *>(ws + lay.chunks);
+    ca.chunk_rank = reinterpret_cast<int *>(ws + lay.ranks);
+    ca.chunk_cost = reinterpret_cast<unsigned long long *>(ws + lay.costs);
+    SplitArgs sa = {};
+    ca.wmax_count = 0;
+    if (weights) {
+        sa.nl = n_layers;
+        for (int k = 0; k < kMaxScales; ++k) {
+            sa.w[k] = weights[k < n_scales ? k : 0];
+            sa.out[k] = reinterpret_cast<uint4 *>(ws + lay.wfrag[k < n_scales ? k : 0]);
+            if (!sa.w[k]) return VFA_ERR_BAD_ARGUMENT;
+        }
+        sa.wmax = reinterpret_cast<unsigned *>(ws + lay.wmax);
+        sa.wexp = reinterpret_cast<int *>(ws + lay.wexp);
+        sa.f16 = (terms == 0 || terms == 2) ? 1 : 0;
+        if (sa.f16) ca.wmax_count = (long long)kC * kC * n_layers; // the partial maxima: spare blocks of the cuts launch
+    }
+    ca.split = sa;
+    // the frame's masks and sub-tile costs in LDS where they fit beside the scan's 8 KB (static)
+    const size_t stage_bytes = (size_t)n_scales * lay.n_tiles * (1 + (size_t)n_views) * 4;
+    ca.staged = stage_bytes <= 144 * 1024 ? 1 : 0;
+    if (ca.staged) {
+        const void *kern = n_frames > 0 ? reinterpret_cast<const void *>(pipe_cuts_kernel<true>) : reinterpret_cast<const void *>(pipe_cuts_kernel<false>);
+        const hipError_t e0 = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
+        if (e0 != hipSuccess) return (int)e0;
+    }
+    const dim3 cgrid(1 + (ca.wmax_count ? kWmaxParts * n_scales : 0));
+    if (n_frames > 0) hipLaunchKernelGGL(pipe_cuts_kernel<true>, cgrid, dim3(1024), ca.staged ? stage_bytes : 0, s, ca);
+    else hipLaunchKernelGGL(pipe_cuts_kernel<false>, cgrid, dim3(1024), ca.staged ? stage_bytes : 0, s, ca);
+    int st = (int)hipGetLastError();
+    if (st) return st;
+    if (weights) {
+        hipLaunchKernelGGL(pipe_split_weight_kernel, dim3(8 * kSteps * 64 / 256, n_scales * n_layers), dim3(256), 0, s, sa);
+        st = (int)hipGetLastError();
+    }
+    return st;
+}
+
+int collapse_impl(const float *const *integrals, const unsigned *const *feat_absmax, const float *const *biases, void *workspace,
+                  size_t workspace_bytes, float *out, int n_views, int L, int W, int n_layers, int n_scales, const int *feat_hw, int accumulate,
+                  int flags, void *stream, int n_frames)
+{
+    const int terms = flags & VFA_FLAG_TERMS_MASK, reserved_cus = (flags >> 8) & 0xff;
+    const int debug = ((flags >> 16) & 0xfff) | ((flags & VFA_FLAG_DUMP_VOX) ? kDbgDumpVox : 0);
+    if (debug && terms != 0 && terms != 2) return VFA_ERR_BAD_ARGUMENT; // (the diagnostic build exists for the default arithmetic only)
+    if (flags & ~(VFA_FLAG_TERMS_MASK | 0xfffff00 | VFA_FLAG_DUMP_VOX)) return VFA_ERR_BAD_ARGUMENT;
+    if (!dims_ok(n_views, L, W, n_layers, n_scales) || !feat_hw || !integrals ||
+        (terms != 0 && terms != 2 && terms != 3 && terms != 4 && terms != 6))
+        return VFA_ERR_BAD_ARGUMENT;
+    const bool f16 = terms == 0 || terms == 2;
+    if (n_views > 32) return VFA_ERR_UNSUPPORTED;
+    const PipeLayout lay = layout_of(n_views, L, W, n_layers, n_scales, n_frames);
+    const int nf = n_frames > 0 ? n_frames : 1;
+    if (lay.n_tiles == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (n_views == 0) {
+        if (!accumulate) return (int)zero_fill(out, (size_t)nf * L * W * kC * sizeof(float), s);
+        return 0;
+    }
+    // (a batched workspace is exactly the size of its batch: one made for another frame count cannot pass)
+    if (!workspace || workspace_bytes < lay.total || (n_frames > 0 && workspace_bytes != lay.total) || !out) return VFA_ERR_BAD_ARGUMENT;
+    unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
+    PipeArgs a;
+    for (int k = 0; k < kMaxScales; ++k) {
+        const int q = k < n_scales ? k : 0;
+        a.sc[k].integral = integrals[q];
+        a.sc[k].bias = biases ? biases[q] : nullptr;
+        a.sc[k].wfrag = reinterpret_cast<const uint4 *>(ws + lay.wfrag[q]);
+        a.sc[k].live = reinterpret_cast<const unsigned *>(ws + lay.live[q]);
+        a.sc[k].shift = reinterpret_cast<const unsigned *>(ws + lay.shifts[q]);
+        a.sc[k].hdrs = ws + lay.hdrs[q];
+        a.sc[k].recs = ws + lay.recs[q];
+        a.sc[k].Hf = feat_hw[2 * q];
+        a.sc[k].Wf = feat_hw[2 * q + 1];
+        if (!a.sc[k].integral) return VFA_ERR_BAD_ARGUMENT;
+        a.sc[k].amax = nullptr; a.sc[k].amax_n = 0;
+    }
+    if (f16 && n_frames > 0) {
+        // batched: the statistics of every frame (its own slice of the stacked ones, or one pass per frame here), then the per-frame
+        // exponents (pipe_frame_exp_kernel); the frame kernel reduces the launch's one statistic per scale
+        FrameExpArgs ea = {};
+        for (int k = 0; k < kMaxScales; ++k) {
+            const int q = k < n_scales ? k : 0;
+            if (feat_absmax && feat_absmax[q]) {
+                ea.amax[k] = feat_absmax[q];
+                ea.count[k] = (int)feature_stats_count(n_views, kC, a.sc[q].Hf);
+                ea.stride[k] = ea.count[k]; // (the statistics are view-major: frame b's views b * n_views ... own a contiguous slice)
+            } else {
+                unsigned *dst = reinterpret_cast<unsigned *>(ws + lay.amax) + (size_t)k * nf * kFallbackStats;
+                if (k < n_scales) {
+                    const size_t img = (size_t)n_views * (a.sc[q].Hf + 2) * (a.sc[q].Wf + 2) * kC;
+                    for (int b = 0; b < nf; ++b) {
+                        const int st = integral_absmax_folded(a.sc[q].integral + (size_t)b * img, dst + (size_t)b * kFallbackStats, n_views, kC,
+                                                              a.sc[q].Hf, a.sc[q].Wf, kFallbackStats, &ea.count[k], stream);
+                        if (st) return st;
+                    }
+                }
+                ea.amax[k] = dst;
+                ea.stride[k] = kFallbackStats;
+            }
+        }
+        ea.dea = reinterpret_cast<unsigned *>(ws + lay.fdea);
+        ea.synth = ea.dea + (size_t)kMaxScales * nf;
+        ea.nf = nf;
+        hipLaunchKernelGGL(pipe_frame_exp_kernel, dim3(n_scales), dim3(256), 0, s, ea);
+        const int st = (int)hipGetLastError();
+        if (st) return st;
+        for (int k = 0; k < kMaxScales; ++k) { a.sc[k].amax = ea.synth + (k < n_scales ? k : 0); a.sc[k].amax_n = 1; }
+    } else if (f16) {
+        // the scale of the fp16 split: what the integral-image call left (feat_absmax), or one pass over the integral images here
+        for (int k = 0; k < n_scales; ++k) {
+            if (feat_absmax && feat_absmax[k]) {
+                a.sc[k].amax = feat_absmax[k];
+                a.sc[k].amax_n = (int)feature_stats_count(n_views, kC, a.sc[k].Hf);
+            } else {
+                unsigned *dst = reinterpret_cast<unsigned *>(ws + lay.amax) + (size_t)k * kFallbackStats;
+                const int st = integral_absmax_folded(a.sc[k].integral, dst, n_views, kC, a.sc[k].Hf, a.sc[k].Wf, kFallbackStats, &a.sc[k].amax_n, stream);
+                if (st) return st;
+                a.sc[k].amax = dst;
+            }
+        }
+        for (int k = n_scales; k < kMaxScales; ++k) { a.sc[k].amax = a.sc[0].amax; a.sc[k].amax_n = a.sc[0].amax_n; }
+    }
+    a.wexp = reinterpret_cast<const int *>(ws + lay.wexp);
+    a.n_scales = n_scales; a.n_views = n_views; a.nl = n_layers; a.L = L; a.W = W; a.tiles_w = lay.tiles_w; a.n_tiles = lay.v_tiles;
+    // (the same for every launch size: the cuts were made once; a batched launch reads the run length its cuts were made for from the
+    // workspace instead -- the batch record of vfa_pipe_batch_records_f32)
+    a.rt = n_frames > 0 ? 0 : frame_run_tiles(n_views, lay.n_tiles, n_scales, n_layers);
+    a.nf = nf;
+    a.fdea = reinterpret_cast<const unsigned *>(ws + lay.fdea);
+    a.meta = reinterpret_cast<const int *>(ws + lay.meta);
+    a.out = out; a.accumulate = accumulate;
+    a.chunk_start = reinterpret_cast<const int *>(ws + lay.chunks);
+    a.chunk_rank = reinterpret_cast<const int *>(ws + lay.ranks);
+    a.partial = reinterpret_cast<float *>(ws + lay.partial);
+    a.slots = reinterpret_cast<float *>(ws + lay.slots);
+    a.n_contrib = contributions_of(n_views);
+    a.tickets = reinterpret_cast<unsigned *>(ws + lay.tickets);
+    a.diag = reinterpret_cast<unsigned long long *>(ws + lay.diag);
+    a.debug = debug;
+    a.balance = reinterpret_cast<int *>(ws + lay.balance);
+    const int nblk = pipe_blocks(lay.v_tiles, reserved_cus);
+    if (debug & kDbgDumpVox) { // (one view, one scale, one layer: `out` has room for exactly one set of voxel features per frame)
+        if (n_views != 1 || n_scales != 1 || n_layers != 1 || accumulate) return VFA_ERR_BAD_ARGUMENT;
+        const hipError_t e0 = hipMemsetAsync(out, 0, (size_t)nf * L * W * kC * sizeof(float), s);
+        if (e0 != hipSuccess) return (int)e0;
+    }
+    if (n_frames > 0) { // (the generic eight-step templates, run length from the workspace)
+        if (debug)
+            hipLaunchKernelGGL((pipe_kernel<2, true, false, false, 0, true>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
+        else if (terms == 4)
+            hipLaunchKernelGGL((pipe_kernel<4, false, false, false, 0, true>), dim3(nblk), dim3(threads_of(4)), 0, s, a);
+        else if (terms == 6)
+            hipLaunchKernelGGL((pipe_kernel<6, false, false, false, 0, true>), dim3(nblk), dim3(threads_of(6)), 0, s, a);
+        else if (terms == 3)
+            hipLaunchKernelGGL((pipe_kernel<3, false, false, false, 0, true>), dim3(nblk), dim3(threads_of(3)), 0, s, a);
+        else
+            hipLaunchKernelGGL((pipe_kernel<2, false, false, false, 0, true>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
+        return (int)hipGetLastError();
+    }
+    // (the tickets are clear: zeroed with the masks by the geometry call, and put back by the last arriver of every earlier launch)
+    const bool small = n_views <= 2 && a.rt == 1; // (groups of at most two sub-tiles: the four-step phase)
+    const bool rt1 = n_views > 2 && a.rt == 1;    // (tile by tile: the tile's sum waits in a slot of the workspace between its groups)
+    if (debug && small && !(debug & kDbgDumpVox)) // (diagnostic build of the default arithmetic)
+        hipLaunchKernelGGL((pipe_kernel<2, true, true>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
+    else if (debug && rt1 && !(debug & kDbgDumpVox))
+        hipLaunchKernelGGL((pipe_kernel<2, true, false, true>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
+    else if (debug)
+        hipLaunchKernelGGL((pipe_kernel<2, true>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
+    else if (terms == 4)
+        hipLaunchKernelGGL((pipe_kernel<4, false>), dim3(nblk), dim3(threads_of(4)), 0, s, a);
+    else if (terms == 6)
+        hipLaunchKernelGGL((pipe_kernel<6, false>), dim3(nblk), dim3(threads_of(6)), 0, s, a);
+    else if (terms == 3 && small)
+        hipLaunchKernelGGL((pipe_kernel<3, false, true>), dim3(nblk), dim3(threads_of(3)), 0, s, a);
+    else if (terms == 3)
+        hipLaunchKernelGGL((pipe_kernel<3, false>), dim3(nblk), dim3(threads_of(3)), 0, s, a);
+    else if (small)
+        hipLaunchKernelGGL((pipe_kernel<2, false, true>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
+    else if (rt1)
+        hipLaunchKernelGGL((pipe_kernel<2, false, false, true>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
+    else if (a.rt == 2)
+        hipLaunchKernelGGL((pipe_kernel<2, false, false, false, 2>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
+    else if (a.rt == 4)
+        hipLaunchKernelGGL((pipe_kernel<2, false, false, false, 4>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
+    else
+        hipLaunchKernelGGL((pipe_kernel<2, false>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
+    return (int)hipGetLastError();
 }
 
 } // namespace
@@ -2038,92 +2383,14 @@ int vfa_pipe_boxes_f32(const float *calibs, const float *grid, const float *z_la
                        int L, int W, int conv_kind, float img_w, float img_h, float cmin, float cmax, int n_scales, const int *feat_hw,
                        int flags, void *workspace, size_t workspace_bytes, void *stream)
 {
-    const int terms = flags & VFA_FLAG_TERMS_MASK;
-    if ((flags & ~VFA_FLAG_TERMS_MASK) || (terms != 0 && terms != 2 && terms != 3 && terms != 4 && terms != 6)) return VFA_ERR_BAD_ARGUMENT;
-    if (!dims_ok(n_views, L, W, n_layers, n_scales) || conv_kind < 0 || conv_kind > 2 || !feat_hw) return VFA_ERR_BAD_ARGUMENT;
-    if (n_views > 32) return VFA_ERR_UNSUPPORTED; // live-view masks are 32 bits wide
-    const PipeLayout lay = layout_of(n_views, L, W, n_layers, n_scales);
-    if (lay.n_tiles == 0 || n_views == 0) return 0;
-    if ((long long)n_views * lay.n_tiles >= (1ll << 31) - 2) return VFA_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < lay.total) return VFA_ERR_BAD_ARGUMENT;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
-    RecordArgs a;
-    a.g = BoxGeom{calibs, grid, z_layers, corner_off, conv_kind, img_w, img_h, cmin, cmax};
-    a.n_views = n_views; a.L = L; a.W = W; a.tiles_w = lay.tiles_w; a.n_tiles = lay.n_tiles; a.n_scales = n_scales; a.nl = n_layers;
-    a.win_slots = terms == 6 ? kWinSlots3 : kWinSlots; // (the kernel variant that will read these records)
-    for (int k = 0; k < kMaxScales; ++k) {
-        a.dims[k].Hf = k < n_scales ? feat_hw[2 * k] : 1;
-        a.dims[k].Wf = k < n_scales ? feat_hw[2 * k + 1] : 1;
-        if (a.dims[k].Hf <= 0 || a.dims[k].Wf <= 0 || a.dims[k].Hf > 65533 || a.dims[k].Wf > 65533) return VFA_ERR_BAD_ARGUMENT;
-        // (tap positions of a direct item are byte offsets into one view's padded image, 32 bits)
-        if ((unsigned long long)(a.dims[k].Hf + 2) * (a.dims[k].Wf + 2) * kSlotBytes >= (1ull << 32)) return VFA_ERR_UNSUPPORTED;
-        a.live[k] = reinterpret_cast<unsigned *>(ws + lay.live[k]);
-        a.shift[k] = reinterpret_cast<unsigned *>(ws + lay.shifts[k]);
-        a.subcost[k] = reinterpret_cast<unsigned *>(ws + lay.subcost[k]);
-        a.hdrs[k] = ws + lay.hdrs[k];
-        a.recs[k] = ws + lay.recs[k];
-    }
-    a.globs = reinterpret_cast<unsigned *>(ws + lay.globs);
-    const hipError_t e = zero_fill(ws, lay.masks_bytes, s); // view masks, tile tickets, counters (a kernel, not hipMemsetAsync: see vfa_geom.h)
-    if (e != hipSuccess) return (int)e;
-    const long long units = (long long)n_views * lay.n_tiles * n_layers; // (view, tile, layer)
-    if ((units + 1) / 2 >= (1ll << 31)) return VFA_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(pipe_records_kernel, dim3((unsigned)((units + 1) / 2)), dim3(kWave), 0, s, a);
-    return (int)hipGetLastError();
+    return boxes_impl(calibs, grid, z_layers, n_layers, corner_off, n_views, L, W, conv_kind, img_w, img_h, cmin, cmax, n_scales, feat_hw, flags,
+                      workspace, workspace_bytes, stream, 0);
 }
 
 int vfa_pipe_cuts_f32(int n_views, int L, int W, int n_layers, int n_scales, const float *const *weights, int flags, void *workspace,
                       size_t workspace_bytes, void *stream)
 {
-    const int terms = flags & VFA_FLAG_TERMS_MASK;
-    if ((flags & ~VFA_FLAG_TERMS_MASK) || (terms != 0 && terms != 2 && terms != 3 && terms != 4 && terms != 6)) return VFA_ERR_BAD_ARGUMENT;
-    if (!dims_ok(n_views, L, W, n_layers, n_scales)) return VFA_ERR_BAD_ARGUMENT;
-    if (n_views > 32) return VFA_ERR_UNSUPPORTED;
-    const PipeLayout lay = layout_of(n_views, L, W, n_layers, n_scales);
-    if (lay.n_tiles == 0 || n_views == 0) return 0;
-    if (!workspace || workspace_bytes < lay.total) return VFA_ERR_BAD_ARGUMENT;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
-    CutArgs ca;
-    for (int k = 0; k < kMaxScales; ++k) ca.live[k] = reinterpret_cast<const unsigned *>(ws + lay.live[k < n_scales ? k : 0]);
-    ca.globs = reinterpret_cast<const unsigned *>(ws + lay.globs);
-    for (int k = 0; k < kMaxScales; ++k) ca.subcost[k] = reinterpret_cast<const unsigned *>(ws + lay.subcost[k < n_scales ? k : 0]);
-    ca.n_scales = n_scales; ca.n_tiles = lay.n_tiles; ca.n_views = n_views; ca.nl = n_layers;
-    ca.rt = frame_run_tiles(n_views, lay.n_tiles, n_scales, n_layers);
-    ca.chunk_start = reinterpret_cast<int *>(ws + lay.chunks);
-    ca.chunk_rank = reinterpret_cast<int *>(ws + lay.ranks);
-    ca.chunk_cost = reinterpret_cast<unsigned long long *>(ws + lay.costs);
-    SplitArgs sa = {};
-    ca.wmax_count = 0;
-    if (weights) {
-        sa.nl = n_layers;
-        for (int k = 0; k < kMaxScales; ++k) {
-            sa.w[k] = weights[k < n_scales ? k : 0];
-            sa.out[k] = reinterpret_cast<uint4 *>(ws + lay.wfrag[k < n_scales ? k : 0]);
-            if (!sa.w[k]) return VFA_ERR_BAD_ARGUMENT;
-        }
-        sa.wmax = reinterpret_cast<unsigned *>(ws + lay.wmax);
-        sa.wexp = reinterpret_cast<int *>(ws + lay.wexp);
-        sa.f16 = (terms == 0 || terms == 2) ? 1 : 0;
-        if (sa.f16) ca.wmax_count = (long long)kC * kC * n_layers; // the partial maxima: spare blocks of the cuts launch
-    }
-    ca.split = sa;
-    // the frame's masks and sub-tile costs in LDS where they fit beside the scan's 8 KB (static)
-    const size_t stage_bytes = (size_t)n_scales * lay.n_tiles * (1 + (size_t)n_views) * 4;
-    ca.staged = stage_bytes <= 144 * 1024 ? 1 : 0;
-    if (ca.staged) {
-        const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(pipe_cuts_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-        if (e0 != hipSuccess) return (int)e0;
-    }
-    hipLaunchKernelGGL(pipe_cuts_kernel, dim3(1 + (ca.wmax_count ? kWmaxParts * n_scales : 0)), dim3(1024), ca.staged ? stage_bytes : 0, s, ca);
-    int st = (int)hipGetLastError();
-    if (st) return st;
-    if (weights) {
-        hipLaunchKernelGGL(pipe_split_weight_kernel, dim3(8 * kSteps * 64 / 256, n_scales * n_layers), dim3(256), 0, s, sa);
-        st = (int)hipGetLastError();
-    }
-    return st;
+    return cuts_impl(n_views, L, W, n_layers, n_scales, weights, flags, workspace, workspace_bytes, stream, 0, nullptr);
 }
 
 int vfa_pipe_balance_f32(int n_views, int L, int W, int n_layers, int n_scales, int reserved_cus, int mode, void *workspace,
@@ -2154,101 +2421,92 @@ int vfa_pipe_collapse_relu_sum_f32(const float *const *integrals, const unsigned
                                    void *workspace, size_t workspace_bytes, float *out, int n_views, int L, int W, int n_layers,
                                    int n_scales, const int *feat_hw, int accumulate, int flags, void *stream)
 {
-    const int terms = flags & VFA_FLAG_TERMS_MASK, reserved_cus = (flags >> 8) & 0xff;
-    const int debug = ((flags >> 16) & 0xfff) | ((flags & VFA_FLAG_DUMP_VOX) ? kDbgDumpVox : 0);
-    if (debug && terms != 0 && terms != 2) return VFA_ERR_BAD_ARGUMENT; // (the diagnostic build exists for the default arithmetic only)
-    if (flags & ~(VFA_FLAG_TERMS_MASK | 0xfffff00 | VFA_FLAG_DUMP_VOX)) return VFA_ERR_BAD_ARGUMENT;
-    if (!dims_ok(n_views, L, W, n_layers, n_scales) || !feat_hw || !integrals ||
-        (terms != 0 && terms != 2 && terms != 3 && terms != 4 && terms != 6))
-        return VFA_ERR_BAD_ARGUMENT;
-    const bool f16 = terms == 0 || terms == 2;
-    if (n_views > 32) return VFA_ERR_UNSUPPORTED;
-    const PipeLayout lay = layout_of(n_views, L, W, n_layers, n_scales);
-    if (lay.n_tiles == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (n_views == 0) {
-        if (!accumulate) return (int)zero_fill(out, (size_t)L * W * kC * sizeof(float), s);
-        return 0;
-    }
-    if (!workspace || workspace_bytes < lay.total || !out) return VFA_ERR_BAD_ARGUMENT;
-    unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
-    PipeArgs a;
+    return collapse_impl(integrals, feat_absmax, biases, workspace, workspace_bytes, out, n_views, L, W, n_layers, n_scales, feat_hw,
+                         accumulate, flags, stream, 0);
+}
+
+// ---- batched frames of a static rig (ABI 9 additions) ----
+size_t vfa_pipe_batch_workspace_bytes(int n_frames, int n_views, int L, int W, int n_layers, int n_scales)
+{
+    if (n_frames < 1 || !dims_ok(n_views, L, W, n_layers, n_scales)) return 0;
+    const PipeLayout lay = layout_of(n_views, L, W, n_layers, n_scales, 1);
+    if ((long long)lay.n_tiles * n_frames >= (1ll << 28)) return 0;
+    return layout_of(n_views, L, W, n_layers, n_scales, n_frames).total;
+}
+
+int vfa_pipe_batch_workspace_layout(int n_frames, int n_views, int L, int W, int n_layers, int n_scales, size_t *offsets, int *tiles)
+{
+    if (vfa_pipe_batch_workspace_bytes(n_frames, n_views, L, W, n_layers, n_scales) == 0 || !offsets || !tiles) return VFA_ERR_BAD_ARGUMENT;
+    const PipeLayout lay = layout_of(n_views, L, W, n_layers, n_scales, n_frames);
     for (int k = 0; k < kMaxScales; ++k) {
-        const int q = k < n_scales ? k : 0;
-        a.sc[k].integral = integrals[q];
-        a.sc[k].bias = biases ? biases[q] : nullptr;
-        a.sc[k].wfrag = reinterpret_cast<const uint4 *>(ws + lay.wfrag[q]);
-        a.sc[k].live = reinterpret_cast<const unsigned *>(ws + lay.live[q]);
-        a.sc[k].shift = reinterpret_cast<const unsigned *>(ws + lay.shifts[q]);
-        a.sc[k].hdrs = ws + lay.hdrs[q];
-        a.sc[k].recs = ws + lay.recs[q];
-        a.sc[k].Hf = feat_hw[2 * q];
-        a.sc[k].Wf = feat_hw[2 * q + 1];
-        if (!a.sc[k].integral) return VFA_ERR_BAD_ARGUMENT;
-        a.sc[k].amax = nullptr; a.sc[k].amax_n = 0;
+        offsets[4 * k + 0] = lay.live[k];
+        offsets[4 * k + 1] = lay.hdrs[k];
+        offsets[4 * k + 2] = lay.recs[k];
+        offsets[4 * k + 3] = lay.wfrag[k];
     }
-    if (f16) {
-        // the scale of the fp16 split: what the integral-image call left (feat_absmax), or one pass over the integral images here
-        for (int k = 0; k < n_scales; ++k) {
-            if (feat_absmax && feat_absmax[k]) {
-                a.sc[k].amax = feat_absmax[k];
-                a.sc[k].amax_n = (int)feature_stats_count(n_views, kC, a.sc[k].Hf);
-            } else {
-                unsigned *dst = reinterpret_cast<unsigned *>(ws + lay.amax) + (size_t)k * kFallbackStats;
-                const int st = integral_absmax_folded(a.sc[k].integral, dst, n_views, kC, a.sc[k].Hf, a.sc[k].Wf, kFallbackStats, &a.sc[k].amax_n, stream);
-                if (st) return st;
-                a.sc[k].amax = dst;
-            }
-        }
-        for (int k = n_scales; k < kMaxScales; ++k) { a.sc[k].amax = a.sc[0].amax; a.sc[k].amax_n = a.sc[0].amax_n; }
-    }
-    a.wexp = reinterpret_cast<const int *>(ws + lay.wexp);
-    a.n_scales = n_scales; a.n_views = n_views; a.nl = n_layers; a.L = L; a.W = W; a.tiles_w = lay.tiles_w; a.n_tiles = lay.n_tiles;
-    a.rt = frame_run_tiles(n_views, lay.n_tiles, n_scales, n_layers); // (the same for every launch size: the cuts were made once)
-    a.out = out; a.accumulate = accumulate;
-    a.chunk_start = reinterpret_cast<const int *>(ws + lay.chunks);
-    a.chunk_rank = reinterpret_cast<const int *>(ws + lay.ranks);
-    a.partial = reinterpret_cast<float *>(ws + lay.partial);
-    a.slots = reinterpret_cast<float *>(ws + lay.slots);
-    a.n_contrib = contributions_of(n_views);
-    a.tickets = reinterpret_cast<unsigned *>(ws + lay.tickets);
-    a.diag = reinterpret_cast<unsigned long long *>(ws + lay.diag);
-    a.debug = debug;
-    a.balance = reinterpret_cast<int *>(ws + lay.balance);
-    const int nblk = pipe_blocks(lay.n_tiles, reserved_cus);
-    if (debug & kDbgDumpVox) { // (one view, one scale, one layer: `out` has room for exactly one set of voxel features)
-        if (n_views != 1 || n_scales != 1 || n_layers != 1 || accumulate) return VFA_ERR_BAD_ARGUMENT;
-        const hipError_t e0 = hipMemsetAsync(out, 0, (size_t)L * W * kC * sizeof(float), s);
-        if (e0 != hipSuccess) return (int)e0;
-    }
-    // (the tickets are clear: zeroed with the masks by the geometry call, and put back by the last arriver of every earlier launch)
-    const bool small = n_views <= 2 && a.rt == 1; // (groups of at most two sub-tiles: the four-step phase)
-    const bool rt1 = n_views > 2 && a.rt == 1;    // (tile by tile: the tile's sum waits in a slot of the workspace between its groups)
-    if (debug && small && !(debug & kDbgDumpVox)) // (diagnostic build of the default arithmetic)
-        hipLaunchKernelGGL((pipe_kernel<2, true, true>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
-    else if (debug && rt1 && !(debug & kDbgDumpVox))
-        hipLaunchKernelGGL((pipe_kernel<2, true, false, true>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
-    else if (debug)
-        hipLaunchKernelGGL((pipe_kernel<2, true>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
-    else if (terms == 4)
-        hipLaunchKernelGGL((pipe_kernel<4, false>), dim3(nblk), dim3(threads_of(4)), 0, s, a);
-    else if (terms == 6)
-        hipLaunchKernelGGL((pipe_kernel<6, false>), dim3(nblk), dim3(threads_of(6)), 0, s, a);
-    else if (terms == 3 && small)
-        hipLaunchKernelGGL((pipe_kernel<3, false, true>), dim3(nblk), dim3(threads_of(3)), 0, s, a);
-    else if (terms == 3)
-        hipLaunchKernelGGL((pipe_kernel<3, false>), dim3(nblk), dim3(threads_of(3)), 0, s, a);
-    else if (small)
-        hipLaunchKernelGGL((pipe_kernel<2, false, true>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
-    else if (rt1)
-        hipLaunchKernelGGL((pipe_kernel<2, false, false, true>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
-    else if (a.rt == 2)
-        hipLaunchKernelGGL((pipe_kernel<2, false, false, false, 2>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
-    else if (a.rt == 4)
-        hipLaunchKernelGGL((pipe_kernel<2, false, false, false, 4>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
-    else
-        hipLaunchKernelGGL((pipe_kernel<2, false>), dim3(nblk), dim3(threads_of(2)), 0, s, a);
+    offsets[12] = lay.tickets;
+    offsets[13] = lay.chunks;
+    offsets[14] = lay.ranks;
+    offsets[15] = lay.diag;
+    offsets[16] = lay.total;
+    offsets[17] = lay.globs;
+    offsets[18] = lay.balance;
+    for (int k = 0; k < kMaxScales; ++k) offsets[19 + k] = lay.shifts[k];
+    offsets[22] = lay.meta;
+    offsets[23] = lay.fdea;
+    tiles[0] = lay.tiles_l;
+    tiles[1] = lay.tiles_w;
+    tiles[2] = kWinSlots;
+    tiles[3] = kChunks;
+    tiles[4] = kWinSlots3;
+    tiles[5] = lay.v_tiles;
+    return 0;
+}
+
+int vfa_pipe_batch_records_f32(const float *calibs, const float *grid, const float *z_layers, int n_layers, const float *corner_off,
+                               int n_views, int L, int W, int conv_kind, float img_w, float img_h, float cmin, float cmax, int n_scales,
+                               const int *feat_hw, const float *const *weights, int n_frames, int flags, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    if (n_frames < 1) return VFA_ERR_BAD_ARGUMENT;
+    if (dims_ok(n_views, L, W, n_layers, n_scales) && vfa_pipe_batch_workspace_bytes(n_frames, n_views, L, W, n_layers, n_scales) == 0)
+        return VFA_ERR_UNSUPPORTED; // (more virtual tiles than the work cuts count in 32 bits)
+    int st = boxes_impl(calibs, grid, z_layers, n_layers, corner_off, n_views, L, W, conv_kind, img_w, img_h, cmin, cmax, n_scales, feat_hw,
+                        flags, workspace, workspace_bytes, stream, n_frames);
+    if (st) return st;
+    int rt = 0;
+    st = cuts_impl(n_views, L, W, n_layers, n_scales, weights, flags, workspace, workspace_bytes, stream, n_frames, &rt);
+    if (st || rt == 0) return st; // (rt == 0: nothing to cut -- no tile or no view)
+    const PipeLayout lay = layout_of(n_views, L, W, n_layers, n_scales, n_frames);
+    hipLaunchKernelGGL(pipe_meta_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
+                       reinterpret_cast<int *>(reinterpret_cast<unsigned char *>(workspace) + lay.meta), n_frames, rt, pipe_blocks(lay.v_tiles, 0),
+                       lay.v_tiles);
     return (int)hipGetLastError();
+}
+
+int vfa_pipe_batch_balance_f32(int n_frames, int n_views, int L, int W, int n_layers, int n_scales, int reserved_cus, int mode,
+                               void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (n_frames < 1 || !dims_ok(n_views, L, W, n_layers, n_scales) || (mode != 0 && mode != 1)) return VFA_ERR_BAD_ARGUMENT;
+    const PipeLayout lay = layout_of(n_views, L, W, n_layers, n_scales, n_frames);
+    if (lay.n_tiles == 0 || n_views == 0) return 0;
+    if (!workspace || workspace_bytes != lay.total) return VFA_ERR_BAD_ARGUMENT;
+    unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
+    hipLaunchKernelGGL(pipe_balance_kernel, dim3(1), dim3(kMaxBlocks), 0, (hipStream_t)stream, reinterpret_cast<int *>(ws + lay.balance),
+                       reinterpret_cast<const int *>(ws + lay.chunks), reinterpret_cast<const unsigned long long *>(ws + lay.costs),
+                       pipe_blocks(lay.v_tiles, reserved_cus), mode);
+    return (int)hipGetLastError();
+}
+
+int vfa_pipe_batch_collapse_relu_sum_f32(const float *const *integrals, const unsigned *const *feat_absmax, const float *const *biases,
+                                         void *workspace, size_t workspace_bytes, float *out, int n_frames, int n_views, int L, int W,
+                                         int n_layers, int n_scales, const int *feat_hw, int accumulate, int flags, void *stream)
+{
+    if (n_frames < 1) return VFA_ERR_BAD_ARGUMENT;
+    if (dims_ok(n_views, L, W, n_layers, n_scales) && vfa_pipe_batch_workspace_bytes(n_frames, n_views, L, W, n_layers, n_scales) == 0)
+        return VFA_ERR_UNSUPPORTED;
+    return collapse_impl(integrals, feat_absmax, biases, workspace, workspace_bytes, out, n_views, L, W, n_layers, n_scales, feat_hw,
+                         accumulate, flags, stream, n_frames);
 }
 
 } // extern "C"

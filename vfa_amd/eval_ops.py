@@ -33,9 +33,22 @@ def bev_nms(heatmap):
     _lib.require_device(heatmap)
     h = heatmap.to(torch.float32).contiguous()
     L, W = h.shape[-2:]
-    assert h.numel() == L * W, "batch 1, one class, like the reference"
+    assert h.numel() == L * W, "batch 1, one class, like the reference (a batch: bev_nms_batch)"
     conf = torch.empty_like(h)
     _lib.call("vfa_bev_nms_f32", _lib.ptr(h), _lib.ptr(conf), L, W, _lib.current_stream_handle())
+    return conf
+
+
+def bev_nms_batch(heatmap):
+    """heatmap (B,1,L,W) logits -> (B,1,L,W): ``bev_nms`` of every frame in one launch (``vfa_bev_nms_batch_f32``); the 5x5 window
+    stops at each frame's edges."""
+    _lib.require_device(heatmap)
+    h = heatmap.to(torch.float32).contiguous()
+    if h.dim() != 4 or h.shape[1] != 1:
+        raise ValueError(f"bev_nms_batch: heatmap must be (B, 1, L, W), got {tuple(h.shape)}")
+    B, _, L, W = h.shape
+    conf = torch.empty_like(h)
+    _lib.call("vfa_bev_nms_batch_f32", _lib.ptr(h), _lib.ptr(conf), B, L, W, _lib.current_stream_handle())
     return conf
 
 
@@ -49,8 +62,10 @@ class BEVDecoder:
         self.grid_size = self.world_size / np.array(cube_LWH)[:2]
         self.dimension_mean = dimension_mean
 
+    _conf = None  # (decode_frames: this frame's slice of the batched NMS)
+
     def nms(self, heatmap):
-        return bev_nms(heatmap)
+        return bev_nms(heatmap) if self._conf is None else self._conf
 
     def _peaks(self, pred):
         heatmap, tytx = pred["heatmap"], pred["loc_offset"]
@@ -90,3 +105,18 @@ class BEVDecoder:
 
     def batch_decode(self, pred, cls_thresh):
         return self.decode3d(pred, cls_thresh) if self.base in ("MultiviewC", "MVM3D") else self.decode2d(pred, cls_thresh)
+
+    def decode_frames(self, pred, cls_thresh):
+        """A batch of B frames (every head (B, ...)) -> a list of B per-frame results, each what ``batch_decode`` gives for that
+        frame alone; the NMS of all frames runs as one launch (``bev_nms_batch``)."""
+        B = pred["heatmap"].shape[0]
+        conf = bev_nms_batch(pred["heatmap"])
+        out = []
+        for b in range(B):
+            one = {k: v[b:b + 1] for k, v in pred.items()}
+            self._conf = conf[b:b + 1]
+            try:
+                out.append(self.batch_decode(one, cls_thresh))
+            finally:
+                self._conf = None
+        return out

@@ -798,3 +798,89 @@ def pipe_workspace_layout(n_views, L, W, n_layers, n_scales):
                tiles_l=int(tiles[0]), tiles_w=int(tiles[1]), max_slots=int(tiles[2]), n_chunks=int(tiles[3]),
                max_slots_3piece=int(tiles[4]), balance=int(off[18]), shifts=[int(off[19 + k]) for k in range(n_scales)])
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# batched frames of a static rig: B frames in one pipelined launch (vfa_pipe.hip, vfa_pipe_batch_*)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def pipe_batch_workspace_bytes(n_frames, n_views, L, W, n_layers, n_scales):
+    """Bytes of the workspace of a batch of ``n_frames`` frames -- exactly: the batched calls refuse any other size."""
+    return int(_lib.lib().vfa_pipe_batch_workspace_bytes(int(n_frames), int(n_views), int(L), int(W), int(n_layers), int(n_scales)))
+
+
+def pipe_batch_workspace_layout(n_frames, n_views, L, W, n_layers, n_scales):
+    """Offsets inside a batched workspace (``pipe_workspace_layout``'s keys + ``meta``, ``frame_exp``, ``virtual_tiles``)."""
+    off = (ctypes.c_size_t * 25)()
+    tiles = (ctypes.c_int * 6)()
+    _lib.call("vfa_pipe_batch_workspace_layout", int(n_frames), int(n_views), int(L), int(W), int(n_layers), int(n_scales), off, tiles)
+    names = ("live", "hdrs", "recs", "wfrag")
+    out = {nm: [int(off[4 * k + i]) for k in range(n_scales)] for i, nm in enumerate(names)}
+    out.update(tickets=int(off[12]), globs=int(off[17]), chunks=int(off[13]), ranks=int(off[14]), diag=int(off[15]), total=int(off[16]),
+               tiles_l=int(tiles[0]), tiles_w=int(tiles[1]), max_slots=int(tiles[2]), n_chunks=int(tiles[3]),
+               max_slots_3piece=int(tiles[4]), balance=int(off[18]), shifts=[int(off[19 + k]) for k in range(n_scales)],
+               meta=int(off[22]), frame_exp=int(off[23]), virtual_tiles=int(tiles[5]))
+    return out
+
+
+def pipe_batch_records(calibs, grid, z_layers, corner_off, conv_kind, image_wh, feat_hws, n_frames, weights=None, crange=(-1, 0.95),
+                       workspace=None, terms=0):
+    """``pipe_records`` for a batch of ``n_frames`` frames of one static rig: the geometry once, the work cuts over the frames' virtual
+    tiles and the batch record -> a workspace of exactly ``pipe_batch_workspace_bytes`` bytes (allocated when ``workspace`` is None,
+    with a cleared balance state)."""
+    _lib.require_device(calibs, grid, z_layers, corner_off)
+    grid = _f32c(grid.reshape(grid.shape[-3], grid.shape[-2], 3))
+    L, W = grid.shape[:2]
+    calibs = _f32c(calibs.reshape(-1, 12))
+    n = calibs.shape[0]
+    z_layers, corner_off = _f32c(z_layers.reshape(-1)), _f32c(corner_off.reshape(8, 3))
+    nl, ns = z_layers.numel(), len(feat_hws)
+    need = pipe_batch_workspace_bytes(n_frames, n, L, W, nl, ns)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=calibs.device)
+        if need > 0:
+            bal = pipe_batch_workspace_layout(n_frames, n, L, W, nl, ns)["balance"]
+            workspace[bal:bal + BALANCE_STATE_BYTES].zero_()
+    wts = None
+    if weights is not None:
+        weights = [_f32c(w) for w in weights]
+        assert len(weights) == ns and all(tuple(w.shape) == (256, 256 * nl) for w in weights)
+        _lib.require_device(*weights)
+        wts = _lib.ptr_array(weights)
+    hw = _lib.int_array([v for f in feat_hws for v in f])
+    _launch("vfa_pipe_batch_records_f32", _lib.ptr(calibs), _lib.ptr(grid), _lib.ptr(z_layers), nl, _lib.ptr(corner_off), n, L, W,
+            int(conv_kind), float(image_wh[0]), float(image_wh[1]), float(crange[0]), float(crange[1]), ns, hw, wts, int(n_frames),
+            int(terms) & 0xf, _lib.ptr(workspace), workspace.numel(), _lib.current_stream_handle(), tag=(int(n_frames), n, L, W, nl, ns))
+    return workspace
+
+
+def pipe_batch_collapse(integrals, biases, workspace, n_frames, grid_lw, n_layers, out=None, accumulate=False, terms=0, reserved_cus=0,
+                        debug=0, absmax=None, dump_vox=False):
+    """out (B, L*W, 256) (+)= per frame sum_scale sum_view relu(vox . W^T + b), B = ``n_frames`` frames in ONE launch of the pipelined
+    kernel.  integrals[k]: (B*n, Hf+2, Wf+2, 256), frame-major; workspace = ``pipe_batch_records`` for the same B."""
+    _lib.require_device(*integrals, workspace, out)
+    ns, B = len(integrals), int(n_frames)
+    L, W = grid_lw
+    if B < 1 or integrals[0].shape[0] % B:
+        raise ValueError(f"pipe_batch_collapse: {integrals[0].shape[0]} integral images are not {B} frames of equal camera count")
+    n = integrals[0].shape[0] // B
+    assert all(i.shape[0] == B * n and i.shape[3] == 256 and i.is_contiguous() and i.dtype == torch.float32 for i in integrals)
+    if out is None:
+        out = torch.empty((B, L * W, 256), dtype=torch.float32, device=integrals[0].device)
+        accumulate = False
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, L * W, 256)
+    biases = [None if b is None else _f32c(b) for b in (biases if biases is not None else [None] * ns)]
+    hw = _lib.int_array([v for i in integrals for v in (i.shape[1] - 2, i.shape[2] - 2)])
+    absmax, absmax_ptrs = _absmax_of(integrals, absmax)
+    _launch("vfa_pipe_batch_collapse_relu_sum_f32", _lib.ptr_array(list(integrals)), absmax_ptrs, _lib.ptr_array(biases),
+            _lib.ptr(workspace), workspace.numel(), _lib.ptr(out), B, n, L, W, int(n_layers), ns, hw, 1 if accumulate else 0,
+            _lib.collapse_flags(terms, reserved_cus) | ((int(debug) & 0xfff) << 16) | (_lib.FLAG_DUMP_VOX if dump_vox else 0),
+            _lib.current_stream_handle(), tag=(B, n, L, W, int(n_layers), tuple((i.shape[1] - 2, i.shape[2] - 2) for i in integrals)))
+    return out
+
+
+def pipe_batch_balance(workspace, n_frames, n_views, grid_lw, n_layers, n_scales, reserved_cus=0, reset=False):
+    """``pipe_balance`` for a batched workspace (``vfa_pipe_batch_balance_f32``)."""
+    _lib.require_device(workspace)
+    L, W = grid_lw
+    _launch("vfa_pipe_batch_balance_f32", int(n_frames), int(n_views), int(L), int(W), int(n_layers), int(n_scales), int(reserved_cus),
+            0 if reset else 1, _lib.ptr(workspace), workspace.numel(), _lib.current_stream_handle())

@@ -322,6 +322,111 @@ def pipe_frame(mods, features, calibs, grid, crange=(-1, 0.95), out=None, accumu
     return out
 
 
+def pipe_frames_ok(mods, n_views, tensors=()):
+    """``pipe_frame_ok`` for a batch of frames of one rig (``pipe_frames``): single-layer grids included -- the batched launch exists
+    in the pipelined kernel only."""
+    m0 = mods[0]
+    if not (PIPE and COLLAPSE_KERNEL != "library" and 1 <= len(mods) <= 3 and 0 < n_views <= 32):
+        return False
+    if not all(m.channel == 256 and m.collapse.out_features == 256 and m.num_grid_layer == m0.num_grid_layer
+               and m.geometry_key == m0.geometry_key and getattr(m.args, "data", None) == getattr(m0.args, "data", None)
+               and tuple(m.args.image_size) == tuple(m0.args.image_size) for m in mods):
+        return False
+    if not torch.is_grad_enabled():
+        return True
+    params = [p for m in mods for p in (m.collapse.weight, m.collapse.bias)] + [t for t in tensors if t is not None]
+    return not any(p.requires_grad for p in params)
+
+
+def pipe_frames(mods, features, calibs, grid, n_frames, crange=(-1, 0.95), out=None, accumulate=False, reserved_cus=0, integrals=None,
+                terms=None):
+    """``pipe_frame`` for a batch of ``n_frames`` frames of ONE static rig, in one launch of the pipelined kernel per band:
+    ``out (B, L*W, 256) (+)=`` per frame ``sum_scale sum_view relu(collapse_scale(vox))``.
+
+    features: one (B*n, 256, Hf, Wf) lateral batch per scale, frame-major (frame b's cameras at rows b*n .. b*n + n - 1); or
+    ``integrals`` (B*n, Hf+2, Wf+2, 256) per scale.  calibs (n, 3, 4): the rig, shared by every frame.  The geometry of the rig is
+    made once for the batch (``ops.pipe_batch_records``: the box records of one frame, the work cuts over the frames' virtual
+    tiles); frame b is computed with the arithmetic of its own ``pipe_frame`` call (only the association of the sums may differ).
+    The persistent workspace, the balance state and the banding over grid rows are ``pipe_frame``'s, keyed on B as well."""
+    terms = COLLAPSE_TERMS if terms is None else int(terms)
+    B = int(n_frames)
+    if integrals is not None:
+        features = [i.permute(0, 3, 1, 2)[:, :, 1:-1, 1:-1] for i in integrals]  # views: only their shapes are read below
+    _lib.require_device(calibs, grid, *features)
+    m0 = mods[0]
+    conv_kind = _conv_kind(m0.args)
+    img_h, img_w = (float(v) for v in m0.args.image_size)
+    if grid.dim() < 3:
+        raise ValueError("pipe_frames needs the grid as (L, W, 3) or (1, L, W, 3): the tiles follow its rows and columns")
+    if calibs.dim() != 3:
+        raise ValueError(f"pipe_frames takes one rig for the whole batch: calibs (n, 3, 4), got {tuple(calibs.shape)}")
+    grid = grid.reshape(grid.shape[-3], grid.shape[-2], 3)
+    length, width = grid.shape[0], grid.shape[1]
+    dev = features[0].device
+    n, nl, ns = calibs.shape[0], m0.num_grid_layer, len(mods)
+    if B < 0 or any(f.shape[0] != B * n for f in features):
+        raise ValueError(f"pipe_frames: every scale needs {B} x {n} maps (frame-major), got {[tuple(f.shape) for f in features]}")
+    if out is None:
+        out = torch.empty((B, length * width, 256), dtype=torch.float32, device=dev)
+        accumulate = False
+    if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (B, length * width, 256):
+        raise ValueError("pipe_frames: out must be a contiguous fp32 (B, L*W, 256) tensor")
+    if B == 0 or length * width == 0:
+        return out
+    z_layers, corner_off = m0._kernel_geometry(dev)
+    feat_hws = [tuple(f.shape[-2:]) for f in features]
+    rows = length
+    while rows > 4 and ops.pipe_batch_workspace_bytes(B, n, rows, width, nl, ns) > PIPE_WS_LIMIT:
+        rows = max(4, ((rows + 1) // 2 + 3) // 4 * 4)
+    with torch.no_grad():
+        cur = _lib.current_stream(dev)
+        side = _side_stream(dev) if SIDE_STREAM and integrals is None and not torch.cuda.is_current_stream_capturing() else cur
+        weights = [m.collapse.weight for m in mods]
+        biases = [m.collapse.bias for m in mods]
+        band_rows = min(rows, length)
+        n_bands = (length + rows - 1) // rows
+        st = _pipe_state(dev, ("frames", B, n, length, width, band_rows, nl, ns, terms, int(reserved_cus), conv_kind, tuple(feat_hws)),
+                         ops.pipe_batch_workspace_bytes(B, n, band_rows, width, nl, ns), n_bands,
+                         layout=lambda: ops.pipe_batch_workspace_layout(B, n, band_rows, width, nl, ns))
+        ws_full = st["ws"]
+        balancing = PIPE_BALANCE and st["frames"] == 0 and not torch.cuda.is_current_stream_capturing()
+        for b, r0 in enumerate(range(0, length, rows)):
+            r1 = min(length, r0 + rows)
+            band = grid[r0:r1]
+            # (a batched workspace is exactly the size of its band's layout: a shorter last band takes the front of it)
+            ws = ws_full if r1 - r0 == band_rows else ws_full[:ops.pipe_batch_workspace_bytes(B, n, r1 - r0, width, nl, ns)]
+            if side is not cur:
+                side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                ops.pipe_batch_records(calibs, band, z_layers, corner_off, conv_kind, (img_w, img_h), feat_hws, B, weights=weights,
+                                       crange=crange, workspace=ws, terms=terms)
+            if integrals is None:
+                integrals = ops.integral_images(features)  # every frame and stride in one launch pair, beside the geometry
+            if side is not cur:
+                cur.wait_stream(side)
+            if n_bands > 1:
+                bal_off = (st["balance_off"] if r1 - r0 == band_rows
+                           else ops.pipe_batch_workspace_layout(B, n, r1 - r0, width, nl, ns)["balance"])
+                ws[bal_off:bal_off + ops.BALANCE_STATE_BYTES].copy_(st["bands"][b], non_blocking=True)
+            if balancing:
+                ops.pipe_batch_balance(ws, B, n, (r1 - r0, width), nl, ns, reserved_cus=reserved_cus)
+                if n_bands > 1:
+                    st["bands"][b].copy_(ws[bal_off:bal_off + ops.BALANCE_STATE_BYTES], non_blocking=True)
+            if n_bands == 1:
+                ops.pipe_batch_collapse(integrals, biases, ws, B, (length, width), nl, out=out, accumulate=accumulate, terms=terms,
+                                        reserved_cus=reserved_cus)
+            else:  # (a band of every frame is not contiguous in `out`: through a buffer of the band)
+                part = ops.pipe_batch_collapse(integrals, biases, ws, B, (r1 - r0, width), nl, terms=terms, reserved_cus=reserved_cus)
+                if accumulate:
+                    out[:, r0 * width:r1 * width] += part
+                else:
+                    out[:, r0 * width:r1 * width] = part
+        st["frames"] += 1
+        if side is not cur:
+            ws_full.record_stream(side)
+    return out
+
+
 # "1" (default): the first frame of a geometry computes balanced work shares for the pipelined kernel's workgroups
 # (`vfa_pipe_balance_f32`), kept with the persistent workspace; "0": the uniform split of the work cuts.
 PIPE_BALANCE = os.environ.get("VFA_AMD_PIPE_BALANCE", "1") == "1"
@@ -355,7 +460,7 @@ class owned_capture_states:
         return False
 
 
-def _pipe_state(dev, key, ws_bytes, n_bands):
+def _pipe_state(dev, key, ws_bytes, n_bands, layout=None):
     # one workspace per (geometry, stream): the geometry call of a frame on another stream must not overwrite records the
     # previous frame's kernel on THIS stream is still reading (`side.wait_stream(cur)` only orders against the current one)
     key = (dev.index, _lib.current_stream(dev).cuda_stream) + key
@@ -375,7 +480,7 @@ def _pipe_state(dev, key, ws_bytes, n_bands):
                 break
     if st is None:
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        lay = ops.pipe_workspace_layout(key[2], key[5], key[4], key[6], key[7])
+        lay = layout() if layout is not None else ops.pipe_workspace_layout(key[2], key[5], key[4], key[6], key[7])
         st = {"ws": ws, "frames": 0, "balance_off": lay["balance"],
               "bands": [torch.zeros(ops.BALANCE_STATE_BYTES, dtype=torch.uint8, device=dev) for _ in range(n_bands)] if n_bands > 1 else None}
         ws[lay["balance"]:lay["balance"] + ops.BALANCE_STATE_BYTES].zero_()  # (= vfa_pipe_balance_f32 mode 0)
@@ -879,7 +984,22 @@ class FrameGeometry:
         self._built.record(_lib.current_stream(dev))
 
     def frame(self, features=None, integrals=None, out=None, accumulate=False):
-        """features: one (n, 256, Hf, Wf) lateral batch per scale (or ``integrals``: their integral images) -> (1, C, L, W)."""
+        """features: one (n, 256, Hf, Wf) lateral batch per scale (or ``integrals``: their integral images) -> (1, C, L, W).
+        A stacked batch of B frames -- (B*n, 256, Hf, Wf) per scale, frame-major -- gives (B, C, L, W), frame by frame on the same
+        geometry (``out``: then (B, L*W, C))."""
+        lead = (integrals if integrals is not None else features)[0].shape[0]
+        if lead != self.n and self.n > 0 and lead % self.n == 0:
+            B = lead // self.n
+            c = self.mods[0].collapse.out_features
+            dev = self.ws.device
+            if out is None:
+                out = torch.empty((B, self.length * self.width, c), dtype=torch.float32, device=dev)
+                accumulate = False
+            for b in range(B):
+                part = slice(b * self.n, (b + 1) * self.n)
+                self.frame(features=None if features is None else [f[part] for f in features],
+                           integrals=None if integrals is None else [i[part] for i in integrals], out=out[b], accumulate=accumulate)
+            return out.view(B, self.length, self.width, c).permute(0, 3, 1, 2)
         if [(m.collapse.weight._version, m.collapse.weight.data_ptr()) for m in self.mods] != self._versions:
             raise RuntimeError("FrameGeometry: a collapse.weight changed since the geometry (which holds its split fragments) was built")
         if (lazy.version_of(self._rig[0]), lazy.version_of(self._rig[1])) != self._rig_versions:

@@ -166,7 +166,11 @@ class VFANet(nn.Module):
         return ops.integral_images([p[0] for p in parts], [p[1] for p in parts], [p[2] for p in parts], channels_last=True)
 
     def ortho_features(self, images, calibs, grid, distributed=False):
-        """The fused BEV map (1,256,L,W) entering the heads (reference vfanet.py:64-82, 131)."""
+        """The fused BEV map (1,256,L,W) entering the heads (reference vfanet.py:64-82, 131).  images (B,N,3,iH,iW): a batch of B
+        frames -> (B,256,L,W); with ONE rig (calibs (N,3,4)) in inference the whole batch is one launch of the pipelined kernel
+        (``aggregate_views(..., frames=B)``), otherwise -- calibs (B,N,3,4), gradients, distributed -- frame by frame."""
+        if images.dim() == 5:
+            return self._ortho_frames(images, calibs, grid, distributed)
         if distributed:
             mine = camera_shard(images.shape[0])
             idx = torch.tensor(mine, dtype=torch.long, device=images.device)
@@ -180,8 +184,24 @@ class VFANet(nn.Module):
         return aggregate_views(self.vfa8, self.vfa16, self.vfa32, lat8, lat16, lat32, calibs, grid, (-1, 0.95),
                                distributed=distributed)
 
+    def _ortho_frames(self, images, calibs, grid, distributed):
+        B, N = images.shape[:2]
+        if calibs.dim() == 4 and tuple(calibs.shape[:2]) != (B, N) or calibs.dim() == 3 and calibs.shape[0] != N:
+            raise ValueError(f"VFANet: images {tuple(images.shape)} need calibs ({N},3,4) or ({B},{N},3,4), got {tuple(calibs.shape)}")
+        mods3 = [self.vfa8, self.vfa16, self.vfa32]
+        if B == 0 or distributed or calibs.dim() == 4 or torch.is_grad_enabled() or not (images.is_cuda and vfa_op.pipe_frames_ok(mods3, N)):
+            outs = [self.ortho_features(images[b], calibs[b] if calibs.dim() == 4 else calibs, grid, distributed) for b in range(B)]
+            return torch.cat(outs, 0) if outs else images.new_zeros(0, 256, grid.shape[-3], grid.shape[-2])
+        flat = images.reshape(B * N, *images.shape[2:])
+        if FUSE_PRODUCER:
+            return aggregate_views(self.vfa8, self.vfa16, self.vfa32, None, None, None, calibs, grid, (-1, 0.95),
+                                   integrals=self.lateral_integrals(flat), frames=B)
+        lat8, lat16, lat32 = self.laterals(flat)
+        return aggregate_views(self.vfa8, self.vfa16, self.vfa32, lat8, lat16, lat32, calibs, grid, (-1, 0.95), frames=B)
+
     def forward(self, images, calibs, grid, visualize=False, visualize_ortho=False, distributed=False):
-        """images (N,3,iH,iW), calibs (N,3,4), grid (1,L,W,3) -> dict like the reference (vfanet.py:141-149)."""
+        """images (N,3,iH,iW), calibs (N,3,4), grid (1,L,W,3) -> dict like the reference (vfanet.py:141-149).
+        images (B,N,3,iH,iW): a batch of B frames, calibs (N,3,4) or (B,N,3,4); the heads run at batch B."""
         if visualize or visualize_ortho:
             self._visualize(images, calibs, grid, boxes=visualize_ortho)
         topdown = self.ortho_features(images, calibs, grid, distributed)
