@@ -205,7 +205,7 @@ int vfa_project_gather_ws_f32(const float *integral, const float *calibs, const 
 /* Backward of vfa_project_gather_f32 with respect to the integral images (training: the reference back-propagates
  * through the path with autograd, trainer.py:41; calib and grid carry no gradient).  grad_vox is layer-major
  * (n_views, cell_count, nl*C); grad_integral (n_views, Hf+2, Wf+2, C) is zeroed first unless VFA_BWD_ACCUMULATE is set in `flags`.
- * Scatter-add with float atomics: results are not bit-reproducible run to run. */
+ * Scatter-add with float atomics: results are not bit-reproducible run to run (vfa_project_gather_backward_det_f32 below is). */
 int vfa_project_gather_backward_f32(const float *grad_vox, const float *calibs, const float *grid, const float *z_layers,
                                     const float *corner_off, float *grad_integral, int n_views, int C, int Hf, int Wf,
                                     int nl, int n_cells, int cell_begin, int cell_count, int conv_kind, float img_w,
@@ -218,6 +218,35 @@ int vfa_project_gather_backward_grid_f32(const float *grad_vox, const float *cal
                                     const float *corner_off, float *grad_integral, int n_views, int C, int Hf, int Wf,
                                     int nl, int n_cells, int cell_begin, int cell_count, int grid_w, int conv_kind, float img_w,
                                     float img_h, float cmin, float cmax, int flags, void *stream);
+
+/* The same backward, bit-reproducible (what the Python layer runs under torch.use_deterministic_algorithms(True)): the arguments of
+ * vfa_project_gather_backward_grid_f32 plus a caller-owned `workspace` of exactly
+ * vfa_gather_backward_det_workspace_bytes(n_views, nl, cell_count, C, Hf, Wf) bytes (a function of the shapes alone: 16 sort
+ * records of 20 bytes, 16 bytes of digit counts and 2 x 16 / 256 gradient rows per box; 0 = shapes beyond 2^31 records or 2^32 taps).
+ * No float atomics: every box stores its 16 (tap, coefficient) records in fixed slots, a stable radix sort orders them by tap, and the
+ * gradient rows of each tap's list are summed in list order (lists cut into fixed runs of 256 sorted positions, whose sums are added
+ * in run order).  Contract:
+ *   - the result is a function of the inputs and shapes only: not of timing, workgroup count, VFA_FLAG_RESERVED_CUS(n) (accepted,
+ *     no effect: no kernel here is persistent), tensor addresses or the process;
+ *   - VFA_BWD_ACCUMULATE: grad_integral = grad_integral + S with exactly one fp32 add per element a box touches, S = what the call
+ *     writes without the flag (elements no box touches are left as they are); without it grad_integral is zeroed first;
+ *   - masked boxes pass nothing: their grad_vox rows are never read and may hold anything;
+ *   - any C, any cell range (grid_w is checked as above and otherwise unused); no stream sync, no device-to-host read;
+ *   - a workspace of another size: VFA_ERR_BAD_ARGUMENT, nothing written.
+ * Same sums as the atomic kernels up to rounding (not bitwise). `flags`: VFA_BWD_ACCUMULATE | VFA_FLAG_RESERVED_CUS(n). */
+size_t vfa_gather_backward_det_workspace_bytes(int n_views, int nl, int cell_count, int C, int Hf, int Wf);
+int vfa_project_gather_backward_det_f32(const float *grad_vox, const float *calibs, const float *grid, const float *z_layers,
+                                        const float *corner_off, float *grad_integral, int n_views, int C, int Hf, int Wf, int nl,
+                                        int n_cells, int cell_begin, int cell_count, int grid_w, int conv_kind, float img_w,
+                                        float img_h, float cmin, float cmax, int flags, void *workspace, size_t workspace_bytes,
+                                        void *stream);
+
+/* Column sums in a fixed order (the bias gradient of the deterministic backward):  out[n] = (accumulate ? out[n] : 0) + S[n],
+ * S[n] = sum over r < rows of x[r, n], x (rows, N) row-major.  A workgroup owns 64 columns; its row slot k < K (K = 64 when 4 | N,
+ * else 16) adds rows k, k + K, ... in row order, then the K slot sums are added pairwise in a fixed tree: bit-reproducible, the
+ * same on every launch.  Accumulate: one add per column.  Parallel over columns only: a tall matrix with few columns is best
+ * summed in two calls, over its (rows / B, B N) view and then over the (B, N) result (ops.column_sum does). */
+int vfa_column_sum_f32(const float *x, float *out, long long rows, int N, int accumulate, void *stream);
 
 /* Backward of vfa_integral_image_f32: reverse cumsum over H (in place on grad_integral, which is destroyed) then over
  * W, written as NCHW grad_feature (n_views, C, Hf, Wf). */

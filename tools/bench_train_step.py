@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Forward + backward of the aggregate on one workload, both training paths: fused forward + recomputing backward
-(`vfa_op.FUSED_TRAIN`, the default) and the unfused kernels with vox / lin saved by autograd."""
+(`vfa_op.FUSED_TRAIN`, the default) and the unfused kernels with vox / lin saved by autograd.  ``--deterministic`` adds the
+bit-reproducible backward (torch.use_deterministic_algorithms(True)), with torch's fill of uninitialised memory on and off."""
 import argparse
 import os
 import sys
@@ -16,6 +17,7 @@ from vfa_amd.synthetic import make_workload  # noqa: E402
 p = argparse.ArgumentParser()
 p.add_argument("--workload", default="multiviewc_200x200x1")
 p.add_argument("--steps", type=int, default=5)
+p.add_argument("--deterministic", action="store_true", help="also time the deterministic mode (fill of torch.empty on and off)")
 a = p.parse_args()
 dev = torch.device("cuda:0")
 wl = make_workload(a.workload, channels=256, seed=0)
@@ -33,21 +35,37 @@ def step():
 
 from vfa_amd import vfa_op  # noqa: E402
 
+import torch.utils.deterministic  # noqa: E402
+
+MODES = [("default", False, None)]
+if a.deterministic:
+    MODES += [("deterministic", True, True), ("deterministic, no fill", True, False)]
+fill0 = torch.utils.deterministic.fill_uninitialized_memory
 for fused in (True, False):
-    vfa_op.FUSED_TRAIN = fused
-    for _ in range(2):
-        step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        step()
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / a.steps
-    with ops.KernelTimer() as kt:
-        step()
+    for mode, det, fill in MODES:
+        vfa_op.FUSED_TRAIN = fused
+        torch.use_deterministic_algorithms(det)
+        if fill is not None:
+            torch.utils.deterministic.fill_uninitialized_memory = fill
+        for _ in range(2):
+            step()
         torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() / 1e9
-    torch.cuda.reset_peak_memory_stats()
-    print(f"{a.workload} {'fused forward + recomputing backward' if fused else 'unfused (vox, lin saved)'}: forward+backward {dt * 1e3:.2f} ms/step, peak memory {peak:.2f} GB")
-    for k, v in kt.summary().items():
-        print(f"  {k}: {v['launches']} launches/step, {v['ms']:.3f} ms/step")
+        torch.cuda.reset_peak_memory_stats()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            step()
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / a.steps
+        peak = torch.cuda.max_memory_allocated() / 1e9
+        with ops.KernelTimer() as kt:
+            step()
+            torch.cuda.synchronize()
+        torch.use_deterministic_algorithms(False)
+        torch.utils.deterministic.fill_uninitialized_memory = fill0
+        print(f"{a.workload} {'fused forward + recomputing backward' if fused else 'unfused (vox, lin saved)'} [{mode}]: "
+              f"forward+backward {dt * 1e3:.2f} ms/step, peak memory {peak:.2f} GB")
+        for k, v in kt.summary().items():
+            print(f"  {k}: {v['launches']} launches/step, {v['ms']:.3f} ms/step")
+            if k in ("vfa_project_gather_backward_det_f32", "vfa_column_sum_f32"):
+                for tag, t in v["by_tag"].items():
+                    print(f"    {tag}: {t['ms'] * 1e3 / t['launches']:.0f} us per call")

@@ -348,12 +348,29 @@ def project_gather_ws(integral, calibs, grid_flat, z_layers, corner_off, conv_ki
     return vox
 
 
+def deterministic_mode(deterministic=None):
+    """The ``deterministic`` keyword of the backward wrappers: None = torch's switch (``torch.use_deterministic_algorithms``)."""
+    return torch.are_deterministic_algorithms_enabled() if deterministic is None else bool(deterministic)
+
+
+_det_ws = {}
+
+
+def det_workspace_bytes(n, nl, cell_count, C, Hf, Wf):
+    """Bytes of the workspace of the deterministic scatter (``vfa_gather_backward_det_workspace_bytes``): a function of the shapes."""
+    return _lib.lib().vfa_gather_backward_det_workspace_bytes(n, nl, cell_count, C, Hf, Wf)
+
+
 def project_gather_backward(grad_vox, integral_shape, calibs, grid_flat, z_layers, corner_off, conv_kind, image_wh,
-                            crange=(-1, 0.95), cell_begin=0, cell_count=None, out=None, accumulate=False, kernel=None, grid_w=0):
+                            crange=(-1, 0.95), cell_begin=0, cell_count=None, out=None, accumulate=False, kernel=None, grid_w=0,
+                            deterministic=None, reserved_cus=0):
     """d vox (n, cell_count, nl*C) layer-major -> d integral (n, Hf+2, Wf+2, C) by scatter-add (float atomics).
     ``kernel="direct"`` selects the per-box atomic kernel instead of the LDS-privatised one (C = 256).  ``grid_w``: cells per row of
     the ground grid the cells come from (row-major; 0 = unknown) -- the LDS-privatised scatter then works on patches of 4 x 8 cells
-    (``vfa_project_gather_backward_grid_f32``) instead of 32 cells in a line."""
+    (``vfa_project_gather_backward_grid_f32``) instead of 32 cells in a line.
+    ``deterministic`` (None = torch's switch): the bit-reproducible sort-and-sum scatter (``vfa_project_gather_backward_det_f32``,
+    no float atomics; ``kernel`` is ignored, ``reserved_cus`` is passed on and changes nothing) with a workspace cached per
+    (device, stream)."""
     _lib.require_device(grad_vox, calibs, grid_flat, z_layers, corner_off, out)
     n, Hp, Wp, C = integral_shape
     n_cells, nl = grid_flat.shape[0], z_layers.numel()
@@ -363,6 +380,22 @@ def project_gather_backward(grad_vox, integral_shape, calibs, grid_flat, z_layer
         out = torch.empty(tuple(integral_shape), dtype=torch.float32, device=grad_vox.device)
         accumulate = False
     grid_w = int(grid_w) if grid_w and n_cells % int(grid_w) == 0 else 0
+    if deterministic_mode(deterministic):
+        dev = grad_vox.device
+        need = det_workspace_bytes(n, nl, cell_count, C, Hp - 2, Wp - 2)
+        if need == 0 and n * nl * cell_count > 0:
+            raise ValueError(f"deterministic scatter: shapes too large for one call ({n} views x {cell_count} cells x {nl} layers)")
+        key = (dev.index, _lib.current_stream(dev).cuda_stream)
+        ws = _det_ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _det_ws[key] = None  # (free the old one first)
+            ws = _det_ws[key] = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        _launch("vfa_project_gather_backward_det_f32", _lib.ptr(grad_vox), _lib.ptr(calibs), _lib.ptr(grid_flat),
+                _lib.ptr(z_layers), _lib.ptr(corner_off), _lib.ptr(out), n, C, Hp - 2, Wp - 2, nl, n_cells, cell_begin,
+                cell_count, grid_w, int(conv_kind), float(image_wh[0]), float(image_wh[1]), float(crange[0]), float(crange[1]),
+                (_lib.BWD_ACCUMULATE if accumulate else 0) | _lib.collapse_flags(0, reserved_cus), _lib.ptr(ws), need,
+                _lib.current_stream_handle(), tag=(n, C, Hp - 2, Wp - 2, nl, cell_count))
+        return out
     _launch("vfa_project_gather_backward_grid_f32", _lib.ptr(grad_vox), _lib.ptr(calibs), _lib.ptr(grid_flat),
             _lib.ptr(z_layers), _lib.ptr(corner_off), _lib.ptr(out), n, C, Hp - 2, Wp - 2, nl, n_cells, cell_begin,
             cell_count, grid_w, int(conv_kind), float(image_wh[0]), float(image_wh[1]), float(crange[0]), float(crange[1]),
@@ -382,20 +415,52 @@ def integral_image_backward(grad_integral):
     return grad_feature
 
 
-def relu_mask_backward(grad, lin, bias):
-    """-> (grad_lin (n,M,N) = grad * (lin + bias > 0), grad_bias (N) or None).  Backward of both epilogues."""
+def relu_mask_backward(grad, lin, bias, deterministic=None):
+    """-> (grad_lin (n,M,N) = grad * (lin + bias > 0), grad_bias (N) or None).  Backward of both epilogues.
+    ``deterministic`` (None = torch's switch): grad_bias from ``column_sum`` (fixed order) instead of the kernel's float atomics."""
     _lib.require_device(grad, lin, bias)
     n, M, N = lin.shape
     grad = _f32c(grad)
+    det = deterministic_mode(deterministic)
     if N % 4 != 0 or 1024 % N != 0:  # shapes outside the kernel's fast path: plain torch on the GPU
         pre = lin if bias is None else lin + bias
         g = grad.unsqueeze(0) * (pre > 0)
-        return g, (None if bias is None else g.sum(dim=(0, 1)))
+        if bias is None:
+            return g, None
+        return g, (column_sum(g.reshape(n * M, N)) if det else g.sum(dim=(0, 1)))
     glin = torch.empty_like(lin)
-    gbias = None if bias is None else torch.empty_like(bias)
+    gbias = None if (bias is None or det) else torch.empty_like(bias)
     _launch("vfa_relu_mask_backward_f32", _lib.ptr(grad), _lib.ptr(lin), _lib.ptr(bias), _lib.ptr(glin), _lib.ptr(gbias),
             n, M, N, _lib.current_stream_handle())
+    if det and bias is not None:
+        gbias = column_sum(glin.view(n * M, N))
     return glin, gbias
+
+
+COLUMN_SUM_WIDTH = 16384  # columns of the first of the two column-sum calls on a tall matrix
+
+
+def column_sum(x, out=None, accumulate=False):
+    """out (N) (+)= column sums of x (rows, N) in a fixed order (``vfa_column_sum_f32``): bit-reproducible, no atomics.  A tall
+    matrix is summed in two calls: over the (rows // B, B N) view of its first rows (B = COLUMN_SUM_WIDTH // N; the kernel is
+    parallel over columns), then over the (B, N) partial sums followed by the remaining rows.  The order is a function of the shape."""
+    _lib.require_device(x, out)
+    x = _f32c(x)
+    rows, N = x.shape
+    if out is None:
+        out = torch.empty(N, dtype=torch.float32, device=x.device)
+        accumulate = False
+    assert tuple(out.shape) == (N,) and out.is_contiguous() and out.dtype == torch.float32
+    B = COLUMN_SUM_WIDTH // N if N % 4 == 0 else 1
+    if B >= 2 and rows >= 4 * B:
+        head = rows // B * B
+        part = torch.empty((B + rows - head, N), dtype=torch.float32, device=x.device)
+        _launch("vfa_column_sum_f32", _lib.ptr(x), _lib.ptr(part), head // B, B * N, 0, _lib.current_stream_handle(), tag=(rows, N))
+        part[B:] = x[head:]
+        x, rows = part, part.shape[0]
+    _launch("vfa_column_sum_f32", _lib.ptr(x), _lib.ptr(out), rows, N, 1 if accumulate else 0, _lib.current_stream_handle(),
+            tag=(rows, N))
+    return out
 
 
 _grad_w_ws = {}
@@ -510,21 +575,23 @@ def collapse_gemm(vox2d, weight, out=None, terms=0, reserved_cus=0):
     return out
 
 
-def collapse_gemm_relu_backward(vox, weight, bias, grad_out, terms=0, reserved_cus=0, absmax=None, shift=None):
+def collapse_gemm_relu_backward(vox, weight, bias, grad_out, terms=0, reserved_cus=0, absmax=None, shift=None, deterministic=None):
     """Training backward behind the fused forward: vox (n, cells, K), weight (256, K) (columns in the order of vox), bias (256) or
     None, grad_out (cells, 256) -> (grad_lin (n, cells, 256) = (vox . W^T + b > 0) ? grad_out : 0, grad_bias (256)) with the ReLU mask
     as the epilogue of the recomputed product (``vfa_collapse_gemm_relu_backward_f32``): the pre-activations never reach memory.
     ``absmax`` (the feature statistics of this scale's integral images, int32) selects the product of the FUSED FRAME KERNELS
     (``vfa_collapse_gemm_relu_backward_f16_f32``: fp16 pieces under the frame's scales); with ``shift`` = this chunk's rows of
-    ``sliver_shifts`` ((n or 1, cells) uint8) the mask is then the forward's bit for bit."""
+    ``sliver_shifts`` ((n or 1, cells) uint8) the mask is then the forward's bit for bit.  ``deterministic`` (None = torch's switch):
+    the kernel gets no bias-gradient pointer and grad_bias comes from ``column_sum`` (fixed order) instead of float atomics."""
     _lib.require_device(vox, weight, bias, grad_out)
+    det = deterministic_mode(deterministic)
     vox, weight, grad_out = _f32c(vox), _f32c(weight), _f32c(grad_out)
     n, cells, K = vox.shape
     assert tuple(weight.shape) == (256, K) and tuple(grad_out.shape) == (cells, 256)
     bias = None if bias is None else _f32c(bias)
     dev = vox.device
     glin = torch.empty((n, cells, 256), dtype=torch.float32, device=dev)
-    gbias = torch.zeros(256, dtype=torch.float32, device=dev)
+    gbias = None if det else torch.zeros(256, dtype=torch.float32, device=dev)
     need = _lib.lib().vfa_collapse_gemm_workspace_bytes(K, 256)
     key = (dev.index, _lib.current_stream(dev).cuda_stream)
     ws = _gemm_ws.get(key)
@@ -543,10 +610,12 @@ def collapse_gemm_relu_backward(vox, weight, bias, grad_out, terms=0, reserved_c
                 _lib.ptr(grad_out), _lib.ptr(glin), _lib.ptr(gbias), _lib.ptr(ws), ws.numel(), n, cells, K, 256, _lib.ptr(absmax),
                 absmax.numel(), _lib.ptr(rows) if rows is not None else None, _lib.ptr(tiles) if tiles is not None else None,
                 _lib.collapse_flags(0, reserved_cus), _lib.current_stream_handle(), tag=(n, cells, K, "f16"))
-        return glin, gbias
-    _launch("vfa_collapse_gemm_relu_backward_f32", _lib.ptr(vox), _lib.ptr(weight), _lib.ptr(bias) if bias is not None else None,
-            _lib.ptr(grad_out), _lib.ptr(glin), _lib.ptr(gbias), _lib.ptr(ws), ws.numel(), n, cells, K, 256,
-            _lib.collapse_flags(terms, reserved_cus), _lib.current_stream_handle(), tag=(n, cells, K))
+    else:
+        _launch("vfa_collapse_gemm_relu_backward_f32", _lib.ptr(vox), _lib.ptr(weight), _lib.ptr(bias) if bias is not None else None,
+                _lib.ptr(grad_out), _lib.ptr(glin), _lib.ptr(gbias), _lib.ptr(ws), ws.numel(), n, cells, K, 256,
+                _lib.collapse_flags(terms, reserved_cus), _lib.current_stream_handle(), tag=(n, cells, K))
+    if det:
+        gbias = column_sum(glin.view(n * cells, 256))
     return glin, gbias
 
 

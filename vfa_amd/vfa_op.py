@@ -581,6 +581,8 @@ class _FusedFrameTrain(torch.autograd.Function):
                 g_w_lm = torch.zeros_like(w_lm) if need_w else None
                 g_b = torch.zeros_like(b) if need_b else None
                 per_cell = n * nl * C * 4 * 2  # vox and d vox
+                if need_lat and ops.deterministic_mode():  # + the workspace of the deterministic scatter (linear in the cells)
+                    per_cell += -(-ops.det_workspace_bytes(n, nl, 1024, C, integral.shape[1] - 2, integral.shape[2] - 2) // 1024)
                 chunk = max(1, min(n_cells, VOX_BYTES_LIMIT // max(per_cell, 1)))
                 # the sliver shifts the forward's geometry pass gave this scale's items (serial kernel: per (view, tile); pipelined: per
                 # tile over views and layers): the recomputed product scales its rows the same way
