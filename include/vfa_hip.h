@@ -203,7 +203,8 @@ int vfa_project_gather_ws_f32(const float *integral, const float *calibs, const 
                               float img_w, float img_h, float cmin, float cmax, int vox_layout, void *stream);
 
 /* Backward of vfa_project_gather_f32 with respect to the integral images (training: the reference back-propagates
- * through the path with autograd, trainer.py:41; calib and grid carry no gradient).  grad_vox is layer-major
+ * through the path with autograd, trainer.py:41; the gradient of calib and grid is vfa_project_gather_backward_geometry_f32's,
+ * below).  grad_vox is layer-major
  * (n_views, cell_count, nl*C); grad_integral (n_views, Hf+2, Wf+2, C) is zeroed first unless VFA_BWD_ACCUMULATE is set in `flags`.
  * Scatter-add with float atomics: results are not bit-reproducible run to run (vfa_project_gather_backward_det_f32 below is). */
 int vfa_project_gather_backward_f32(const float *grad_vox, const float *calibs, const float *grid, const float *z_layers,
@@ -240,6 +241,35 @@ int vfa_project_gather_backward_det_f32(const float *grad_vox, const float *cali
                                         int n_cells, int cell_begin, int cell_count, int grid_w, int conv_kind, float img_w,
                                         float img_h, float cmin, float cmax, int flags, void *workspace, size_t workspace_bytes,
                                         void *stream);
+
+/* Backward of vfa_project_gather_f32 with respect to the GEOMETRY: the camera matrices and the ground grid (the reference's
+ * autograd differentiates vfa_op.py:64-119 with respect to calib and grid whenever they require grad).  Inputs: grad_vox layer-major
+ * (n_views, cell_count, nl*C), the zero-bordered channels-last integral images the forward pooled from, and the geometry arguments and
+ * cell range of the gather.  Outputs, either may be NULL:
+ *   grad_calibs (n_views, 12) = d L / d calibs (row-major 3 x 4 per view), summed over the range's cells and layers;
+ *   grad_grid   (cell_count, 3) = d L / d grid of the cells cell_begin .. cell_begin + cell_count - 1 (grid units: the world-unit
+ *               gradient times the conversion's scale, 1 MultiviewC, 1/40 MultiviewX, 2.5 Wildtrack), summed over views and layers.
+ * Per box: the corners are projected again with the forward's exact fp32 sequence (so the min / max, clamp and visibility decisions
+ * are the forward's); the box edges get d vox . d vox / d edge from the 16 taps the forward pools (grid_sample's derivative with
+ * respect to the sample point, and the area term); each edge's gradient goes to the corner torch.min / max selects (lowest index on
+ * ties), through the clamp (passed where cmin <= value <= cmax), the normalisation and the perspective division.  z_layers and
+ * corner_off get no gradient.  Contract:
+ *   - bit-reproducible, no float atomics: the result is a function of the inputs and shapes only (a wave owns 8 cells and walks their
+ *     views and layers in a fixed order; per-view partials go to fixed slots of `workspace` and are summed in slot order);
+ *   - VFA_BWD_ACCUMULATE: out = out + S with exactly one fp32 add per element, S = what the call writes without the flag;
+ *   - masked boxes pass nothing: their grad_vox rows are never read;
+ *   - a box with a NaN corner (a camera plane through the cube) is masked in the forward and passes NOTHING here, where the
+ *     reference's autograd would carry NaN into calib.grad and grid.grad: a deliberate difference (the gradient stays finite);
+ *   - any C, any cell range; no stream sync, no device-to-host read;
+ *   - `workspace`: at least vfa_gather_backward_geometry_workspace_bytes(n_views, cell_count) bytes when grad_calibs is non-NULL
+ *     (48 bytes per view and 8 cells, rounded up to 256), otherwise unused (may be NULL).
+ * `flags`: VFA_BWD_ACCUMULATE. */
+size_t vfa_gather_backward_geometry_workspace_bytes(int n_views, int cell_count);
+int vfa_project_gather_backward_geometry_f32(const float *grad_vox, const float *integral, const float *calibs, const float *grid,
+                                             const float *z_layers, const float *corner_off, float *grad_calibs, float *grad_grid,
+                                             int n_views, int C, int Hf, int Wf, int nl, int n_cells, int cell_begin, int cell_count,
+                                             int conv_kind, float img_w, float img_h, float cmin, float cmax, int flags, void *workspace,
+                                             size_t workspace_bytes, void *stream);
 
 /* Column sums in a fixed order (the bias gradient of the deterministic backward):  out[n] = (accumulate ? out[n] : 0) + S[n],
  * S[n] = sum over r < rows of x[r, n], x (rows, N) row-major.  A workgroup owns 64 columns; its row slot k < K (K = 64 when 4 | N,

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Forward + backward of the aggregate on one workload, both training paths: fused forward + recomputing backward
 (`vfa_op.FUSED_TRAIN`, the default) and the unfused kernels with vox / lin saved by autograd.  ``--deterministic`` adds the
-bit-reproducible backward (torch.use_deterministic_algorithms(True)), with torch's fill of uninitialised memory on and off."""
+bit-reproducible backward (torch.use_deterministic_algorithms(True)), with torch's fill of uninitialised memory on and off.
+``--geometry-grad`` adds a step with calibs and grid requiring grad (vfa_project_gather_backward_geometry_f32 per scale and chunk)."""
 import argparse
 import os
 import sys
@@ -18,6 +19,7 @@ p = argparse.ArgumentParser()
 p.add_argument("--workload", default="multiviewc_200x200x1")
 p.add_argument("--steps", type=int, default=5)
 p.add_argument("--deterministic", action="store_true", help="also time the deterministic mode (fill of torch.empty on and off)")
+p.add_argument("--geometry-grad", action="store_true", help="also time a step with calibs and grid requiring grad")
 a = p.parse_args()
 dev = torch.device("cuda:0")
 wl = make_workload(a.workload, channels=256, seed=0)
@@ -37,13 +39,17 @@ from vfa_amd import vfa_op  # noqa: E402
 
 import torch.utils.deterministic  # noqa: E402
 
-MODES = [("default", False, None)]
+MODES = [("default", False, None, False)]
 if a.deterministic:
-    MODES += [("deterministic", True, True), ("deterministic, no fill", True, False)]
+    MODES += [("deterministic", True, True, False), ("deterministic, no fill", True, False, False)]
+if a.geometry_grad:
+    MODES += [("geometry grad", False, None, True)]
 fill0 = torch.utils.deterministic.fill_uninitialized_memory
 for fused in (True, False):
-    for mode, det, fill in MODES:
+    for mode, det, fill, geo in MODES:
         vfa_op.FUSED_TRAIN = fused
+        calibs.requires_grad_(geo)
+        grid.requires_grad_(geo)
         torch.use_deterministic_algorithms(det)
         if fill is not None:
             torch.utils.deterministic.fill_uninitialized_memory = fill
@@ -66,6 +72,6 @@ for fused in (True, False):
               f"forward+backward {dt * 1e3:.2f} ms/step, peak memory {peak:.2f} GB")
         for k, v in kt.summary().items():
             print(f"  {k}: {v['launches']} launches/step, {v['ms']:.3f} ms/step")
-            if k in ("vfa_project_gather_backward_det_f32", "vfa_column_sum_f32"):
+            if k in ("vfa_project_gather_backward_det_f32", "vfa_column_sum_f32", "vfa_project_gather_backward_geometry_f32"):
                 for tag, t in v["by_tag"].items():
                     print(f"    {tag}: {t['ms'] * 1e3 / t['launches']:.0f} us per call")

@@ -52,6 +52,10 @@ SIGNATURES = {
     "vfa_project_gather_backward_det_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                                             _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_float, _c_int, _vp,
                                             _c_size_t, _vp],
+    "vfa_gather_backward_geometry_workspace_bytes": [_c_int, _c_int],
+    "vfa_project_gather_backward_geometry_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                                 _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_float, _c_int, _vp, _c_size_t,
+                                                 _vp],
     "vfa_column_sum_f32": [_vp, _vp, _c_longlong, _c_int, _c_int, _vp],
     "vfa_integral_image_backward_f32": [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp],
     "vfa_relu_mask_backward_f32": [_vp, _vp, _vp, _vp, _vp, _c_int, _c_size_t, _c_int, _vp],

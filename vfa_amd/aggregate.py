@@ -90,7 +90,10 @@ def all_reduce_prehead_grads(module, group=None, prefixes=PREHEAD_PREFIXES):
     all-reduce (backbone ``base``, laterals ``lat*`` / ``bn*``, projectors ``vfa*``) were only exercised by the local
     cameras, so their gradients are partial sums: this SUMs them over ranks (not a mean -- DistributedDataParallel's
     averaging would scale them by 1/world against the heads; a rank with no camera contributes zeros).  Without it
-    the replicas diverge.  Returns the number of tensors reduced."""
+    the replicas diverge.  Returns the number of tensors reduced.
+    Camera matrices that require grad are not parameters of the module and are NOT summed here: each rank's ``calibs.grad`` holds the
+    rows of its own cameras (``camera_shard``) and zeros in the others' rows; a caller that wants every row on every rank sums it
+    itself.  The same holds for ``grid.grad``: it is the share of this rank's cameras."""
     if not (dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1):
         return 0
     params = [p for n, p in module.named_parameters() if p.requires_grad and n.startswith(tuple(prefixes))]
@@ -226,7 +229,7 @@ def _aggregate_frames(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, cran
     if B == 0:
         return torch.zeros((0, c_out, length, width), dtype=torch.float32, device=grid.device)
     if (calibs.dim() == 3 and not distributed and n > 0
-            and vfa_op.pipe_frames_ok(mods3, n, () if integrals is not None else (lat8, lat16, lat32))):
+            and vfa_op.pipe_frames_ok(mods3, n, (calibs, grid) + (() if integrals is not None else (lat8, lat16, lat32)))):
         ortho = vfa_op.pipe_frames(mods3, None if integrals is not None else [lat8, lat16, lat32], calibs, grid, B, crange,
                                    integrals=integrals)
         return ortho.view(B, length, width, c_out).permute(0, 3, 1, 2)
@@ -274,14 +277,14 @@ def aggregate_views(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange
         ortho = torch.empty((length * width, vfa8.collapse.out_features), dtype=torch.float32, device=grid.device)
         frame = vfa_op.pipe_frame if vfa_op.pipe_frame_ok(mods3, n) else vfa_op.fused_frame
         frame(mods3, None, calibs, grid, crange, out=ortho, reserved_cus=reserved, integrals=integrals)  # (an ops.IntegralImages keeps its feature statistics)
-    elif n > 0 and vfa_op.fused_train_ok(mods3, n, (lat8, lat16, lat32)):
+    elif n > 0 and vfa_op.fused_train_ok(mods3, n, (lat8, lat16, lat32), (calibs, grid)):
         # training: the fused kernel in the forward, voxel features and pre-activations recomputed scale by scale in the backward
         ortho = vfa_op.fused_frame_train(mods3, [lat8, lat16, lat32], calibs, grid, crange, reserved_cus=reserved)
-    elif n > 0 and vfa_op.pipe_frame_ok(mods3, n, (lat8, lat16, lat32)):
+    elif n > 0 and vfa_op.pipe_frame_ok(mods3, n, (lat8, lat16, lat32, calibs, grid)):
         # inference, any number of z-layers: geometry once per frame + ONE persistent kernel (pooling waves beside matrix waves)
         ortho = torch.empty((length * width, vfa8.collapse.out_features), dtype=torch.float32, device=grid.device)
         vfa_op.pipe_frame(mods3, [lat8, lat16, lat32], calibs, grid, crange, out=ortho, reserved_cus=reserved)
-    elif n > 0 and all(m.mfma_collapse_ok(lat) for m, lat in work):
+    elif n > 0 and all(m.mfma_collapse_ok(lat, (calibs, grid)) for m, lat in work):
         # inference on single-layer grids: per scale, pooling then ONE MFMA kernel that forms collapse + bias + ReLU and
         # sums the views into the map (sum over views per scale, then over scales: the reference's sums re-associated,
         # inside the post-GEMM tolerance)

@@ -77,6 +77,35 @@ __device__ __forceinline__ void project_corner(const BoxGeom &g, const float *__
     nv = (2.0f * w) / g.img_h; nv = nv - 1.0f; nv = clamp_t(nv, g.cmin, g.cmax);
 }
 
+// The same corner for the geometry backward (vfa_geom_grad.hip): the identical instruction sequence -- so nu / nv, and with them the
+// min / max, clamp and visibility decisions, are the forward's bit for bit -- plus what the chain rule needs: the world point X, the
+// homogeneous h = P [X 1] and the values in front of the clamp.  `project_corner` itself is left as it is (the forward is pinned).
+__device__ __forceinline__ void project_corner_ex(const BoxGeom &g, const float *__restrict__ P, float gx, float gy, float gz, int k,
+                                                  float &nu, float &nv, float &nu_pre, float &nv_pre, float (&X)[3], float (&h)[3])
+{
+    float x = gx + g.corner_off[k * 3 + 0];
+    float y = gy + g.corner_off[k * 3 + 1];
+    float z = gz + g.corner_off[k * 3 + 2];
+    if (g.conv_kind == VFA_CONV_MULTIVIEWX) {
+        x = x / 40.0f; y = y / 40.0f; z = z / 40.0f;
+    } else if (g.conv_kind == VFA_CONV_WILDTRACK) {
+        x = x * 2.5f; x = x - 300.0f;
+        y = y * 2.5f; y = y - 900.0f;
+        z = z * 2.5f;
+    }
+    X[0] = x; X[1] = y; X[2] = z;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const float a0 = P[r * 4 + 0] * x, a1 = P[r * 4 + 1] * y, a2 = P[r * 4 + 2] * z;
+        float s = a0 + a1;
+        s = s + a2;
+        h[r] = s + P[r * 4 + 3];
+    }
+    const float u = h[0] / h[2], w = h[1] / h[2];
+    nu_pre = (2.0f * u) / g.img_w; nu_pre = nu_pre - 1.0f; nu = clamp_t(nu_pre, g.cmin, g.cmax);
+    nv_pre = (2.0f * w) / g.img_h; nv_pre = nv_pre - 1.0f; nv = clamp_t(nv_pre, g.cmin, g.cmax);
+}
+
 __device__ __forceinline__ float box_area(float l, float t, float r, float b, int Hf, int Wf)
 {
     const float dx = r - l, dy = b - t;

@@ -404,6 +404,55 @@ def project_gather_backward(grad_vox, integral_shape, calibs, grid_flat, z_layer
     return out
 
 
+def project_gather_backward_geometry(grad_vox, integral, calibs, grid_flat, z_layers, corner_off, conv_kind, image_wh,
+                                     crange=(-1, 0.95), cell_begin=0, cell_count=None, grad_calibs=None, grad_grid=None, want_calibs=True,
+                                     want_grid=True, accumulate=False):
+    """d vox (n, cell_count, nl*C) layer-major -> (d calibs (n, 12), d grid (cell_count, 3)) of the box pooling
+    (``vfa_project_gather_backward_geometry_f32``: bit-reproducible, no float atomics, whatever torch's deterministic switch says).
+    ``integral``: the zero-bordered channels-last images (n, Hf+2, Wf+2, C) the forward pooled from.  ``grad_calibs`` / ``grad_grid``:
+    outputs to write (``accumulate``: add, one fp32 add per element -- then every wanted output must be given, ValueError otherwise);
+    without ``accumulate`` a missing one is allocated when ``want_*``.  Returns the pair
+    (an entry is None when it was neither given nor wanted)."""
+    if integral.dim() != 4:
+        raise ValueError(f"integral must be (n, Hf+2, Wf+2, C), got {tuple(integral.shape)}")
+    n, Hp, Wp, C = integral.shape
+    if Hp < 3 or Wp < 3:
+        raise ValueError(f"integral must be zero-bordered (n, Hf+2, Wf+2, C), got {tuple(integral.shape)}")
+    if tuple(calibs.shape) != (n, 12):
+        raise ValueError(f"calibs must be ({n}, 12), got {tuple(calibs.shape)}")
+    if grid_flat.dim() != 2 or grid_flat.shape[1] != 3:
+        raise ValueError(f"grid_flat must be (n_cells, 3), got {tuple(grid_flat.shape)}")
+    n_cells, nl = grid_flat.shape[0], z_layers.numel()
+    cell_count = n_cells - cell_begin if cell_count is None else cell_count
+    if cell_begin < 0 or cell_count < 0 or cell_begin + cell_count > n_cells:
+        raise ValueError(f"cell range [{cell_begin}, {cell_begin + cell_count}) outside the {n_cells} cells")
+    if tuple(grad_vox.shape) != (n, cell_count, nl * C):
+        raise ValueError(f"grad_vox must be ({n}, {cell_count}, {nl * C}), got {tuple(grad_vox.shape)}")
+    for name, t, shape in (("grad_calibs", grad_calibs, (n, 12)), ("grad_grid", grad_grid, (cell_count, 3))):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous fp32 {shape}, got {tuple(t.shape)} {t.dtype}")
+    _lib.require_device(grad_vox, integral, calibs, grid_flat, z_layers, corner_off, grad_calibs, grad_grid)  # (shapes first, then the device)
+    dev = grad_vox.device
+    if accumulate and ((grad_calibs is None and want_calibs) or (grad_grid is None and want_grid)):
+        raise ValueError("accumulate=True adds into the outputs: pass every wanted one (grad_calibs / grad_grid), or want_*=False")
+    if grad_calibs is None and want_calibs:
+        grad_calibs = torch.empty((n, 12), dtype=torch.float32, device=dev)
+    if grad_grid is None and want_grid:
+        grad_grid = torch.empty((cell_count, 3), dtype=torch.float32, device=dev)
+    if grad_calibs is None and grad_grid is None:
+        return None, None
+    acc = bool(accumulate)
+    grad_vox, integral, calibs, grid_flat = _f32c(grad_vox), _f32c(integral), _f32c(calibs), _f32c(grid_flat)
+    need = int(_lib.lib().vfa_gather_backward_geometry_workspace_bytes(n, cell_count)) if grad_calibs is not None else 0
+    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev) if need else None
+    _launch("vfa_project_gather_backward_geometry_f32", _lib.ptr(grad_vox), _lib.ptr(integral), _lib.ptr(calibs),
+            _lib.ptr(grid_flat), _lib.ptr(z_layers), _lib.ptr(corner_off), _lib.ptr(grad_calibs), _lib.ptr(grad_grid), n, C, Hp - 2,
+            Wp - 2, nl, n_cells, cell_begin, cell_count, int(conv_kind), float(image_wh[0]), float(image_wh[1]), float(crange[0]),
+            float(crange[1]), _lib.BWD_ACCUMULATE if acc else 0, _lib.ptr(ws), need, _lib.current_stream_handle(),
+            tag=(n, C, Hp - 2, Wp - 2, nl, cell_count))
+    return grad_calibs, grad_grid
+
+
 def integral_image_backward(grad_integral):
     """d integral (n, Hf+2, Wf+2, C) -> d feature (n, C, Hf, Wf).  Destroys ``grad_integral`` (scans it in place)."""
     _lib.require_device(grad_integral)

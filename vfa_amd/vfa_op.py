@@ -88,19 +88,31 @@ class _BoxPool(torch.autograd.Function):
         conv_kind, img_w, img_h, cmin, cmax = geom[:5]
         vox = ops.project_gather(integral, calibs, grid_flat, z_layers, corner_off, conv_kind, (img_w, img_h),
                                  (cmin, cmax), cell_begin, cell_count, _lib.VOX_LAYER_MAJOR)
-        ctx.save_for_backward(calibs, grid_flat, z_layers, corner_off)
+        # (the integral images only when the geometry gradient is wanted: its kernel reads the taps again)
+        geometry = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        ctx.save_for_backward(calibs, grid_flat, z_layers, corner_off, *((integral,) if geometry else ()))
         ctx.meta = (geom, tuple(integral.shape), cell_begin, cell_count)
         return vox
 
     @staticmethod
     def backward(ctx, grad_vox):
-        calibs, grid_flat, z_layers, corner_off = ctx.saved_tensors
+        calibs, grid_flat, z_layers, corner_off = ctx.saved_tensors[:4]
         geom, shape, cell_begin, cell_count = ctx.meta
         conv_kind, img_w, img_h, cmin, cmax = geom[:5]
-        grad_integral = ops.project_gather_backward(grad_vox, shape, calibs, grid_flat, z_layers, corner_off, conv_kind,
-                                                    (img_w, img_h), (cmin, cmax), cell_begin, cell_count,
-                                                    grid_w=geom[5] if len(geom) > 5 else 0)
-        return grad_integral, None, None, None, None, None, None, None
+        need_cal, need_grid = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        grad_integral = g_cal = g_grid = None
+        if ctx.needs_input_grad[0] or not (need_cal or need_grid):
+            grad_integral = ops.project_gather_backward(grad_vox, shape, calibs, grid_flat, z_layers, corner_off, conv_kind,
+                                                        (img_w, img_h), (cmin, cmax), cell_begin, cell_count,
+                                                        grid_w=geom[5] if len(geom) > 5 else 0)
+        if need_cal or need_grid:  # d calibs (n, 12) and d grid of the chunk's cells (vfa_project_gather_backward_geometry_f32)
+            g_cal, g_cells = ops.project_gather_backward_geometry(grad_vox, ctx.saved_tensors[4], calibs, grid_flat, z_layers, corner_off,
+                                                                  conv_kind, (img_w, img_h), (cmin, cmax), cell_begin, cell_count,
+                                                                  want_calibs=need_cal, want_grid=need_grid)
+            if need_grid:
+                g_grid = torch.zeros(grid_flat.shape, dtype=torch.float32, device=grid_flat.device)
+                g_grid[cell_begin:cell_begin + cell_count] = g_cells
+        return grad_integral, g_cal, g_grid, None, None, None, None, None
 
 
 class _CollapseGemm(torch.autograd.Function):
@@ -226,7 +238,8 @@ PIPE_WS_LIMIT = int(os.environ.get("VFA_AMD_PIPE_WS_BYTES", str(3 << 30)))
 
 def pipe_frame_ok(mods, n_views, tensors=()):
     """The pipelined per-frame inference path covers these projector modules (one per feature scale; any layer count, the
-    same for all) for this many cameras, and no gradient is wanted."""
+    same for all) for this many cameras, and no gradient is wanted (of the weights, biases or ``tensors``: pass the features and
+    the geometry -- calibs, grid -- of the call)."""
     m0 = mods[0]
     if not (PIPE and COLLAPSE_KERNEL != "library" and 1 <= len(mods) <= 3 and 0 < n_views <= 32):
         return False
@@ -324,7 +337,7 @@ def pipe_frame(mods, features, calibs, grid, crange=(-1, 0.95), out=None, accumu
 
 def pipe_frames_ok(mods, n_views, tensors=()):
     """``pipe_frame_ok`` for a batch of frames of one rig (``pipe_frames``): single-layer grids included -- the batched launch exists
-    in the pipelined kernel only."""
+    in the pipelined kernel only.  ``tensors``: the features and the geometry (calibs, grid) of the call -- no gradient may be wanted."""
     m0 = mods[0]
     if not (PIPE and COLLAPSE_KERNEL != "library" and 1 <= len(mods) <= 3 and 0 < n_views <= 32):
         return False
@@ -570,10 +583,15 @@ class _FusedFrameTrain(torch.autograd.Function):
         n_cells, nl, C = grid_flat.shape[0], m0.num_grid_layer, 256
         grad_out = grad_out.contiguous()
         g_lats, g_ws, g_bs = [], [], []
+        # the geometry gradient (calibs, grid): every scale's share added into one buffer, scales and chunks in order
+        need_cal, need_grid = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_geo = need_cal or need_grid
+        g_cal = torch.zeros((n, 12), dtype=torch.float32, device=dev) if need_cal else None
+        g_grid = torch.zeros((n_cells, 3), dtype=torch.float32, device=dev) if need_grid else None
         with torch.no_grad():
             for k, (m, integral, w, b, stat) in enumerate(zip(mods, integrals, weights, biases, stats)):
                 need_lat, need_w, need_b = ctx.needs_input_grad[5 + k], ctx.needs_input_grad[5 + ns + k], ctx.needs_input_grad[5 + 2 * ns + k]
-                if not (need_lat or need_w or need_b):
+                if not (need_lat or need_w or need_b or need_geo):
                     g_lats.append(None), g_ws.append(None), g_bs.append(None)
                     continue
                 w_lm = w.view(C, C, nl).permute(0, 2, 1).reshape(C, nl * C).contiguous()  # column layer * C + c, like the pooled rows
@@ -610,17 +628,26 @@ class _FusedFrameTrain(torch.autograd.Function):
                     g2 = g_lin.view(n * count, C)
                     if need_w:
                         ops.grad_weight(g2, vox.view(n * count, nl * C), out=g_w_lm, accumulate=True)
-                    if need_lat:
+                    if need_lat or need_geo:
                         g_vox = ops.grad_input(g2, w_lm).view(n, count, nl * C)
-                        ops.project_gather_backward(g_vox, tuple(integral.shape), cal, grid_flat, z_layers, corner_off, conv_kind,
-                                                    (img_w, img_h), crange, cell_begin=begin, cell_count=count, out=g_int,
-                                                    accumulate=True, grid_w=grid.shape[-2] if grid.dim() >= 3 else 0)
+                        if need_lat:
+                            ops.project_gather_backward(g_vox, tuple(integral.shape), cal, grid_flat, z_layers, corner_off, conv_kind,
+                                                        (img_w, img_h), crange, cell_begin=begin, cell_count=count, out=g_int,
+                                                        accumulate=True, grid_w=grid.shape[-2] if grid.dim() >= 3 else 0)
+                        if need_geo:
+                            ops.project_gather_backward_geometry(g_vox, integral, cal, grid_flat, z_layers, corner_off, conv_kind,
+                                                                 (img_w, img_h), crange, cell_begin=begin, cell_count=count,
+                                                                 grad_calibs=g_cal, want_calibs=False,
+                                                                 grad_grid=None if g_grid is None else g_grid[begin:begin + count],
+                                                                 want_grid=False, accumulate=True)
                         del g_vox
                     del vox, g_lin
                 g_lats.append(ops.integral_image_backward(g_int) if need_lat else None)
                 g_ws.append(g_w_lm.view(C, nl, C).permute(0, 2, 1).reshape(C, C * nl) if need_w else None)
                 g_bs.append(g_b)
-        return (None, None, None, None, None, *g_lats, *g_ws, *g_bs)
+        d_calibs = g_cal.view(calibs.shape).to(calibs.dtype) if need_cal else None
+        d_grid = g_grid.view(grid.shape).to(grid.dtype) if need_grid else None
+        return (d_calibs, d_grid, None, None, None, *g_lats, *g_ws, *g_bs)
 
 
 def fused_frame_train(mods, features, calibs, grid, crange=(-1, 0.95), reserved_cus=0):
@@ -630,14 +657,15 @@ def fused_frame_train(mods, features, calibs, grid, crange=(-1, 0.95), reserved_
     return _FusedFrameTrain.apply(calibs, grid, tuple(crange), tuple(mods), reserved_cus, *tensors)
 
 
-def fused_train_ok(mods, n_views, features):
-    """Gradients are wanted and the fused per-frame kernels cover the forward."""
+def fused_train_ok(mods, n_views, features, geometry=()):
+    """Gradients are wanted -- of the weights, biases, ``features`` or the ``geometry`` tensors (calibs, grid) -- and the fused
+    per-frame kernels cover the forward."""
     if not (FUSED_TRAIN and torch.is_grad_enabled() and _frame_kernels_cover(mods, n_views)):
         return False
     if not (PIPE or (mods[0].num_grid_layer == 1 and FUSED_POOL)):
         return False
     tensors = [p for m in mods for p in (m.collapse.weight, m.collapse.bias)] + [f for f in features if f is not None]
-    return any(t.requires_grad for t in tensors)
+    return any(t.requires_grad for t in tensors) or any(t is not None and t.requires_grad for t in geometry)
 
 
 def window_frame(mods, features, calibs, grid, crange=(-1, 0.95), out=None, accumulate=False, reserved_cus=0):
@@ -754,7 +782,8 @@ class VFA(nn.Module):
         if n_cells == 0 or n == 0:
             return features.new_zeros((n, n_cells, self.collapse.out_features))
         integral = _IntegralImage.apply(features)
-        needs_grad = torch.is_grad_enabled() and (features.requires_grad or self.collapse.weight.requires_grad)
+        needs_grad = torch.is_grad_enabled() and (features.requires_grad or self.collapse.weight.requires_grad
+                                                  or calibs.requires_grad or grid_flat.requires_grad)
         if USE_FUSED and not needs_grad and C == 256 and self.collapse.out_features == 256:
             # inference: pooling feeds the fp32-MFMA collapse product through LDS, vox never reaches HBM
             w_t = self.layer_major_weight().t().contiguous()
@@ -775,13 +804,14 @@ class VFA(nn.Module):
             outs.append(lin.view(n, count, -1))
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 
-    def mfma_collapse_ok(self, features=None):
-        """True when the inference-only bf16-split MFMA kernel (`vfa_collapse_relu_sum_f32`) covers this module."""
+    def mfma_collapse_ok(self, features=None, geometry=()):
+        """True when the inference-only bf16-split MFMA kernel (`vfa_collapse_relu_sum_f32`) covers this module and no gradient
+        is wanted (of the weights, bias, ``features`` or the ``geometry`` tensors: calibs, grid)."""
         if COLLAPSE_KERNEL == "library" or self.num_grid_layer * self.channel != 256 or self.collapse.out_features != 256:
             return False
         if not torch.is_grad_enabled():
             return True
-        params = (self.collapse.weight, self.collapse.bias) + (() if features is None else (features,))
+        params = (self.collapse.weight, self.collapse.bias) + (() if features is None else (features,)) + tuple(geometry)
         return not any(p is not None and p.requires_grad for p in params)
 
     def project_sum(self, features, calibs, grid, crange=(-1, 0.95), out=None, accumulate=False, reserved_cus=0):
@@ -844,9 +874,9 @@ class VFA(nn.Module):
             return lazy.DeferredOrtho([(self, feature, lazy.version_of(feature), calib, lazy.version_of(calib))], grid,
                                       (float(crange[0]), float(crange[1])), (1, self.collapse.out_features, length, width),
                                       feature.device)
-        if grid.dim() >= 3 and fused_train_ok([self], 1, (feature,)):
+        if grid.dim() >= 3 and fused_train_ok([self], 1, (feature,), (calib, grid)):
             ortho = fused_frame_train([self], [feature], calib.reshape(1, 3, 4), grid, crange)
-        elif self.mfma_collapse_ok(feature) or (grid.dim() >= 3 and pipe_frame_ok([self], 1, (feature,))):
+        elif self.mfma_collapse_ok(feature, (calib, grid)) or (grid.dim() >= 3 and pipe_frame_ok([self], 1, (feature, calib, grid))):
             ortho = self.project_sum(feature, calib.reshape(1, 3, 4), grid, crange)
         else:
             lin = self.project_views(feature, calib.reshape(1, 3, 4), grid, crange)
