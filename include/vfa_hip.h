@@ -302,6 +302,33 @@ int vfa_scale_view_sum_f32(const float *lin8, const float *lin16, const float *l
                            const float *bias16, const float *bias32, float *ortho, int n_views, size_t M, int N,
                            int accumulate, void *stream);
 
+/* Scale sum, then a MAXIMUM over views where the reference adds them (view_reduce="max"):
+ *   t_v   = (relu(lin8[v]+b8) + relu(lin16[v]+b16)) + relu(lin32[v]+b32)     fp32, vfanet.py:79's order
+ *   ortho = max over v of t_v, elementwise, views scanned in index order;  argmax[m, c] = the winning view (uint8)
+ * The winner is torch.max(dim=0)'s index: the LOWEST view attaining the maximum (exact ties go to the first view), and a NaN in
+ * any t_v makes the element NaN with the first NaN view as its winner.  n_views = 0 writes zeros (and winner 0), like the sum.
+ *   lin* (n_views, M, N) = vox . W_s^T without bias; bias* (N) or NULL; ortho (M, N); argmax (M, N) bytes, or NULL to skip.
+ * Limits: 0 <= n_views <= 256 (the winner is one byte), N > 0 (VFA_ERR_BAD_ARGUMENT otherwise, or for a NULL lin / ortho).
+ * With 4 | N and 16-byte aligned lin / ortho (4-byte aligned argmax) one thread owns 4 channels; otherwise one channel.
+ * The result is exact (a selection of the fp32 t_v): the same bits on every run.  Across processes that each hold some views
+ * (a MAX all-reduce of the partial maps), ties resolve as here only through a global-index reduction of the winners
+ * (vfa_amd.aggregate._AllReduceMax); a NaN's winner there is unspecified. */
+int vfa_scale_view_max_f32(const float *lin8, const float *lin16, const float *lin32, const float *bias8, const float *bias16,
+                           const float *bias32, float *ortho, uint8_t *argmax, int n_views, size_t M, int N, void *stream);
+
+/* Backward of vfa_scale_view_max_f32 with respect to lin* and bias*:
+ *   w = argmax[m, c];  grad_lin_s[w, m, c] = grad[m, c] * (lin_s[w, m, c] + b_s[c] > 0)  (strict: ReLU's gradient at 0 is 0);
+ *   grad_lin_s[v, m, c] = 0 for every other view v.  Dense (n_views, M, N) rows, zeros included (the product backward reads them).
+ * Only the winner's lin values are read.  A winner >= n_views (not one the forward writes) passes no gradient.
+ * grad_bias* (N): the column sums of grad_lin_s over its n_views * M rows, in a fixed order (vfa_column_sum_f32; parallel over
+ * columns only -- a caller with tall rows passes NULL and sums them itself, ops.scale_view_max_backward does); NULL to skip.
+ * No float atomics anywhere: the results are bit-reproducible whatever the caller's determinism setting.
+ * Limits and error codes as for the forward (VFA_ERR_BAD_ARGUMENT also for a NULL grad / lin / argmax / grad_lin). */
+int vfa_scale_view_max_backward_f32(const float *grad, const float *lin8, const float *lin16, const float *lin32, const float *bias8,
+                                    const float *bias16, const float *bias32, const uint8_t *argmax, float *grad_lin8,
+                                    float *grad_lin16, float *grad_lin32, float *grad_bias8, float *grad_bias16, float *grad_bias32,
+                                    int n_views, size_t M, int N, void *stream);
+
 /* `collapse` + ReLU + view sum in one MFMA kernel, for K = N = 256 (single-layer grids, C = 256):
  *   out[m, :] = (accumulate ? out[m, :] : 0) + sum_v relu(vox[v, m, :] . weight^T + bias)
  *                                              replaces vfa_op.py:121-124 (Linear, ReLU) and vfanet.py:82 (view sum)

@@ -6,7 +6,13 @@ scale go through one launch of each kernel and one fused epilogue forms
 
     ortho = sum_cam ((relu(lin8+b8) + relu(lin16+b16)) + relu(lin32+b32))        (same association order)
 
-Multi-GPU: cameras are sharded over ranks (``camera_shard``); every rank forms the partial sum of its
+``view_reduce="max"`` fuses the cameras by an elementwise maximum of their per-camera maps instead:
+
+    ortho = max_cam ((relu(lin8+b8) + relu(lin16+b16)) + relu(lin32+b32))
+
+with the gradient going to the lowest camera that attains the maximum (torch.max(dim=0)'s index).
+
+Multi-GPU: cameras are sharded over ranks (``camera_shard``); every rank forms the partial sum (max) of its
 cameras and one RCCL all-reduce over xGMI fuses the grid (``all_reduce_ortho``).  The reference has no
 distributed code; this is the data-parallel axis the path offers.
 """
@@ -55,6 +61,38 @@ class _ScaleViewSum(torch.autograd.Function):
         return (*outs, *bias_grads)
 
 
+class _ScaleViewMax(torch.autograd.Function):
+    """ortho (M,N) = max over views of the scale sum; the winner per element (uint8 (M,N)) is the second, non-differentiable output."""
+
+    @staticmethod
+    def forward(ctx, lin8, lin16, lin32, b8, b16, b32):
+        ortho, argmax = ops.scale_view_max(lin8, lin16, lin32, b8, b16, b32)
+        ctx.save_for_backward(lin8, lin16, lin32, b8, b16, b32, argmax)
+        ctx.mark_non_differentiable(argmax)
+        return ortho, argmax
+
+    @staticmethod
+    def backward(ctx, grad, _grad_argmax):
+        lin8, lin16, lin32, b8, b16, b32, argmax = ctx.saved_tensors
+        want = ctx.needs_input_grad
+        outs = ops.scale_view_max_backward(grad, lin8, lin16, lin32, b8, b16, b32, argmax, want_bias=want[3:6])
+        return tuple(g if w else None for g, w in zip(outs, want))
+
+
+VIEW_REDUCES = ("sum", "max")
+
+
+def check_view_reduce(view_reduce):
+    if view_reduce not in VIEW_REDUCES:
+        raise ValueError(f"view_reduce must be one of {VIEW_REDUCES}, got {view_reduce!r}")
+    return view_reduce
+
+
+def world_of(group=None):
+    """Ranks in ``group`` (1 without a process group)."""
+    return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+
+
 def camera_shard(n_cam, rank=None, world=None):
     """Cameras owned by ``rank``: rank, rank+world, ... (one camera per GPU when world >= n_cam)."""
     if rank is None:
@@ -76,6 +114,41 @@ class _AllReduceSum(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad):
         return grad, None
+
+
+_NO_CAMERA = torch.iinfo(torch.int32).max  # (the winner map's "not mine" entry: above every camera index)
+
+
+class _AllReduceMax(torch.autograd.Function):
+    """y = max over ranks of x, the per-rank maps of ``view_reduce="max"``; cameras are sharded by ``camera_shard`` (local camera j of
+    group rank r is global camera r + j * world).  Backward: each element's gradient goes only to the rank holding its GLOBAL winning
+    camera, the lowest camera index attaining the maximum, as on one GPU.  A rank maps its local winner to its global index where its
+    local max equals the global max (a sentinel elsewhere) and one MIN all-reduce of that int map names the winner everywhere.  Every
+    rank must run the backward (the training contract: all ranks back-propagate the same loss).  NaN: which rank wins is unspecified.
+    ``argmax`` (M,N) uint8: the local winner of ``_ScaleViewMax``; ``n_local``: the cameras of this rank (0: it owns no element)."""
+
+    @staticmethod
+    def forward(ctx, x, argmax, n_local, group):
+        y = x.detach().clone()
+        dist.all_reduce(y, op=dist.ReduceOp.MAX, group=group)
+        ctx.group, ctx.n_local = group, int(n_local)
+        ctx.save_for_backward(x.detach(), y, argmax)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, y, argmax = ctx.saved_tensors
+        group = ctx.group
+        world, rank = dist.get_world_size(group), dist.get_rank(group)
+        if ctx.n_local > 0:
+            mine = argmax.to(torch.int32) * world + rank
+            mine = torch.where(x == y, mine, torch.full_like(mine, _NO_CAMERA))
+        else:
+            mine = torch.full(x.shape, _NO_CAMERA, dtype=torch.int32, device=x.device)
+        winner = mine.clone()
+        dist.all_reduce(winner, op=dist.ReduceOp.MIN, group=group)
+        keep = (mine == winner) & (mine != _NO_CAMERA)
+        return torch.where(keep, grad, torch.zeros_like(grad)), None, None, None
 
 
 PREHEAD_PREFIXES = ("base.", "lat8.", "lat16.", "lat32.", "bn8.", "bn16.", "bn32.", "vfa8.", "vfa16.", "vfa32.")
@@ -112,21 +185,25 @@ def all_reduce_prehead_grads(module, group=None, prefixes=PREHEAD_PREFIXES):
     return len(params)
 
 
-def all_reduce_ortho(ortho_nhwc, group=None):
-    """Sum the partial BEV maps of all ranks in place (RCCL over xGMI; backend string "nccl" on ROCm)."""
+def all_reduce_ortho(ortho_nhwc, group=None, op=dist.ReduceOp.SUM):
+    """Sum the partial BEV maps of all ranks in place (RCCL over xGMI; backend string "nccl" on ROCm).  ``op=ReduceOp.MAX``: their
+    maximum, without autograd (training in max mode goes through ``_AllReduceMax``, which needs the local winners)."""
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
         if ortho_nhwc.requires_grad:
+            if op != dist.ReduceOp.SUM:
+                raise ValueError("all_reduce_ortho: only the sum is differentiable here; max mode trains through _AllReduceMax")
             return _AllReduceSum.apply(ortho_nhwc, group)
-        dist.all_reduce(ortho_nhwc, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(ortho_nhwc, op=op, group=group)
     return ortho_nhwc
 
 
-def reduce_ortho(ortho_nhwc, dst=0, group=None):
+def reduce_ortho(ortho_nhwc, dst=0, group=None, op=dist.ReduceOp.SUM):
     """Sum the partial BEV maps onto rank ``dst`` OF THE GROUP only (the BEV heads then run on one rank): half the traffic of an
     all-reduce.  Other ranks get their buffer back with unspecified contents.  Returns the tensor.  (``dst`` is a group rank:
-    ``torch.distributed.reduce`` wants the global one, and a sub-group need not contain global rank ``dst``.)"""
+    ``torch.distributed.reduce`` wants the global one, and a sub-group need not contain global rank ``dst``.)  ``op``: the reduction
+    (``ReduceOp.MAX`` in max mode)."""
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
-        dist.reduce(ortho_nhwc, dst=dist.get_global_rank(group, dst) if group is not None else dst, op=dist.ReduceOp.SUM, group=group)
+        dist.reduce(ortho_nhwc, dst=dist.get_global_rank(group, dst) if group is not None else dst, op=op, group=group)
     return ortho_nhwc
 
 
@@ -142,7 +219,7 @@ def row_bands(length, world):
     return [(min(length, r * per), min(length, (r + 1) * per)) for r in range(world)], per
 
 
-def reduce_scatter_ortho(ortho_nhwc, length, width, halo=0, group=None):
+def reduce_scatter_ortho(ortho_nhwc, length, width, halo=0, group=None, op=dist.ReduceOp.SUM):
     """Sum the partial maps and leave every rank with ONE band of BEV rows (+ ``halo`` rows of its neighbours on either side):
     the BEV heads are convolutions with a receptive field of a few rows, so each rank can run their CONVOLUTIONS on its band and
     only the small head outputs are gathered -- a reduce-scatter moves (p - 1) / p of the map once instead of the all-reduce's
@@ -153,7 +230,8 @@ def reduce_scatter_ortho(ortho_nhwc, length, width, halo=0, group=None):
 
     ortho_nhwc (L*W, C) partial map of this rank.  Returns ``(band, (row0, row1), (top, bottom))``: band ((row1 - row0 + top +
     bottom) * W, C) holds rows [row0 - top, row1 + bottom) of the fused map; top / bottom <= halo are the halo rows that exist
-    (none beyond the map's edges).  Without a process group the whole map is the band."""
+    (none beyond the map's edges).  Without a process group the whole map is the band.  ``op``: the reduction (``ReduceOp.MAX`` in
+    max mode; the zero rows that pad the map to equal shares are below every value of a max-mode map)."""
     if not (dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1):
         return ortho_nhwc, (0, length), (0, 0)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
@@ -166,10 +244,10 @@ def reduce_scatter_ortho(ortho_nhwc, length, width, halo=0, group=None):
     mine = ortho_nhwc.new_empty((per * width, c))
     if dist.get_backend(group) == "gloo":  # (CPU tests: gloo has no reduce-scatter; same result through an all-reduce)
         full = padded.clone()
-        dist.all_reduce(full, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(full, op=op, group=group)
         mine.copy_(full[rank * per * width:(rank + 1) * per * width])
     else:
-        dist.reduce_scatter_tensor(mine, padded, op=dist.ReduceOp.SUM, group=group)
+        dist.reduce_scatter_tensor(mine, padded, op=op, group=group)
     r0, r1 = bands[rank]
     mine = mine[:(r1 - r0) * width]
     if halo <= 0:
@@ -216,7 +294,8 @@ class PendingOrtho:
         return self._ortho.view(1, length, width, c).permute(0, 3, 1, 2)
 
 
-def _aggregate_frames(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange, reduce_group, distributed, integrals, halo, B):
+def _aggregate_frames(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange, reduce_group, distributed, integrals, halo, B,
+                      view_reduce="sum"):
     length, width = grid.shape[-3], grid.shape[-2]
     c_out = vfa8.collapse.out_features
     mods3 = [vfa8, vfa16, vfa32]
@@ -228,7 +307,7 @@ def _aggregate_frames(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, cran
         raise ValueError(f"aggregate_views(frames={B}): every scale needs {B} x {n} maps, frame-major")
     if B == 0:
         return torch.zeros((0, c_out, length, width), dtype=torch.float32, device=grid.device)
-    if (calibs.dim() == 3 and not distributed and n > 0
+    if (view_reduce == "sum" and calibs.dim() == 3 and not distributed and n > 0
             and vfa_op.pipe_frames_ok(mods3, n, (calibs, grid) + (() if integrals is not None else (lat8, lat16, lat32)))):
         ortho = vfa_op.pipe_frames(mods3, None if integrals is not None else [lat8, lat16, lat32], calibs, grid, B, crange,
                                    integrals=integrals)
@@ -239,12 +318,12 @@ def _aggregate_frames(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, cran
         one = [None if m is None else m[part] for m in ((lat8, lat16, lat32) if integrals is None else (None, None, None))]
         outs.append(aggregate_views(vfa8, vfa16, vfa32, *one, calibs[b] if calibs.dim() == 4 else calibs, grid, crange,
                                     reduce_group=reduce_group, distributed=distributed, halo=halo,
-                                    integrals=None if integrals is None else [i[part] for i in integrals]))
+                                    integrals=None if integrals is None else [i[part] for i in integrals], view_reduce=view_reduce))
     return torch.cat(outs, 0)
 
 
 def aggregate_views(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange=(-1, 0.95), reduce_group=None,
-                    distributed=False, integrals=None, halo=None, frames=None):
+                    distributed=False, integrals=None, halo=None, frames=None, view_reduce="sum"):
     """The camera loop of ``VFANet.forward`` for the cameras held by this process.
 
     lat* (n,C,h,w) lateral maps of the local cameras, calibs (n,3,4), grid (1,L,W,3)
@@ -260,10 +339,17 @@ def aggregate_views(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange
     ``frames=B``: a batch of B frames -> (B,C,L,W).  lat* (or ``integrals``) hold B*n maps, frame-major; calibs is ONE rig (n,3,4)
     for every frame, or (B,n,3,4) a rig per frame.  One rig and inference: ONE launch of the pipelined kernel for the whole batch
     (``vfa_op.pipe_frames``); anything else -- a rig per frame, gradients, distributed reductions -- runs frame by frame and stacks.
+    ``view_reduce``: ``"sum"`` (the reference's ``ortho += vfa_feats``) or ``"max"``: the elementwise maximum of the cameras'
+    per-camera maps, each element's gradient going to the lowest camera attaining it.  Max mode runs the per-scale
+    path (``project_views`` + ``vfa_scale_view_max_f32``), frame by frame for ``frames=B``, and its ranks reduce with MAX; it takes no
+    ``integrals``.  At most 256 cameras per call.
     """
+    check_view_reduce(view_reduce)
+    if view_reduce == "max" and integrals is not None:
+        raise ValueError('aggregate_views(view_reduce="max") takes the lateral maps, not integrals (no per-frame kernel fuses the max)')
     if frames is not None:
         return _aggregate_frames(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange, reduce_group, distributed, integrals,
-                                 halo, int(frames))
+                                 halo, int(frames), view_reduce)
     length, width = grid.shape[-3], grid.shape[-2]
     n = calibs.shape[0]
     # a per-call flag of the MFMA entry points (include/vfa_hip.h: VFA_FLAG_RESERVED_CUS), no library state
@@ -271,7 +357,16 @@ def aggregate_views(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange
                                 and dist.get_world_size(reduce_group) > 1) else 0
     work = ((vfa8, lat8), (vfa16, lat16), (vfa32, lat32))
     mods3 = [vfa8, vfa16, vfa32]
-    if integrals is not None:
+    argmax = None
+    if view_reduce == "max":
+        # per scale: batched projection + the collapse product (differentiable: _BoxPool, _CollapseGemm), then ONE kernel for the
+        # biases, ReLUs, scale sum and the maximum over cameras (the frame kernels reduce views inside a scale: they cannot)
+        if n > 0:
+            lins = [m.project_views(lat, calibs, grid, crange, reserved_cus=reserved) for m, lat in work]
+            ortho, argmax = _ScaleViewMax.apply(*lins, vfa8.collapse.bias, vfa16.collapse.bias, vfa32.collapse.bias)
+        else:  # a rank without cameras: zeros, below every camera's map
+            ortho = torch.zeros((length * width, vfa8.collapse.out_features), dtype=torch.float32, device=grid.device)
+    elif integrals is not None:
         assert n > 0 and not torch.is_grad_enabled() and (vfa_op.pipe_frame_ok(mods3, n) or vfa_op.fused_frame_ok(mods3, n)), \
             "integral-image inputs need a per-frame inference path"
         ortho = torch.empty((length * width, vfa8.collapse.out_features), dtype=torch.float32, device=grid.device)
@@ -323,23 +418,33 @@ def aggregate_views(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange
     else:  # a rank without cameras (8 GPUs, 7 cameras) contributes zeros
         ortho = torch.zeros((length * width, vfa8.collapse.out_features), dtype=torch.float32, device=grid.device)
     c_out = vfa8.collapse.out_features
+    op = dist.ReduceOp.MAX if view_reduce == "max" else dist.ReduceOp.SUM
     if distributed in ("async", "async_reduce"):
         # ("async_reduce": the sum lands on rank 0 only -- the rank that runs the heads --, half the traffic of the all-reduce; the
         # other ranks' maps are unspecified after the wait)
         work = None
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(reduce_group) > 1:
             if distributed == "async":
-                work = dist.all_reduce(ortho, op=dist.ReduceOp.SUM, group=reduce_group, async_op=True)
+                work = dist.all_reduce(ortho, op=op, group=reduce_group, async_op=True)
             else:
                 dst = dist.get_global_rank(reduce_group, 0) if reduce_group is not None else 0
-                work = dist.reduce(ortho, dst=dst, op=dist.ReduceOp.SUM, group=reduce_group, async_op=True)
+                work = dist.reduce(ortho, dst=dst, op=op, group=reduce_group, async_op=True)
         return PendingOrtho(ortho, work, (length, width, c_out))
     if distributed == "reduce":  # the fused map on rank 0 only (the caller runs the heads there)
-        ortho = reduce_ortho(ortho, 0, reduce_group)
+        ortho = reduce_ortho(ortho, 0, reduce_group, op=op)
     elif distributed == "reduce_scatter":  # this rank's band of BEV rows + the heads' halo: (band (1,C,rows,W), rows, halo)
-        band, rows, halo = reduce_scatter_ortho(ortho, length, width, halo=HEAD_HALO_ROWS if halo is None else int(halo), group=reduce_group)
+        band, rows, halo = reduce_scatter_ortho(ortho, length, width, halo=HEAD_HALO_ROWS if halo is None else int(halo), group=reduce_group,
+                                                op=op)
         n_rows = rows[1] - rows[0] + halo[0] + halo[1]
         return band.view(1, n_rows, width, c_out).permute(0, 3, 1, 2), rows, halo
+    elif distributed and view_reduce == "max" and torch.is_grad_enabled() and world_of(reduce_group) > 1:
+        # training: every rank joins the backward's winner reduction (a rank without cameras or gradients too), so every rank's map
+        # enters _AllReduceMax as a node of the graph
+        if not ortho.requires_grad:
+            ortho = ortho.detach().requires_grad_()
+        if argmax is None:
+            argmax = torch.zeros(ortho.shape, dtype=torch.uint8, device=ortho.device)
+        ortho = _AllReduceMax.apply(ortho, argmax, n, reduce_group)
     elif distributed:
-        ortho = all_reduce_ortho(ortho, reduce_group)
+        ortho = all_reduce_ortho(ortho, reduce_group, op=op)
     return ortho.view(1, length, width, c_out).permute(0, 3, 1, 2)

@@ -583,6 +583,48 @@ def scale_view_sum(lin8, lin16, lin32, b8, b16, b32, out=None, accumulate=False)
     return out
 
 
+MAX_VIEWS = 256  # the winner index of the max fusion is one byte
+
+
+def scale_view_max(lin8, lin16, lin32, b8, b16, b32, out=None, want_argmax=True):
+    """-> (ortho (M,N) = max_v ((relu(lin8+b8) + relu(lin16+b16)) + relu(lin32+b32)), argmax (M,N) uint8 or None).
+    The winner is torch.max(dim=0)'s: the lowest view attaining the maximum, the first NaN view if any (``vfa_scale_view_max_f32``)."""
+    _lib.require_device(lin8, lin16, lin32, b8, b16, b32, out)
+    n, M, N = lin8.shape
+    if tuple(lin16.shape) != (n, M, N) or tuple(lin32.shape) != (n, M, N):
+        raise ValueError(f"scale_view_max: lin shapes differ: {tuple(lin8.shape)}, {tuple(lin16.shape)}, {tuple(lin32.shape)}")
+    if n > MAX_VIEWS:
+        raise ValueError(f"scale_view_max: {n} views, at most {MAX_VIEWS}")
+    lin8, lin16, lin32 = _f32c(lin8), _f32c(lin16), _f32c(lin32)
+    b8, b16, b32 = (None if b is None else _f32c(b) for b in (b8, b16, b32))
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=lin8.device)
+    argmax = torch.empty((M, N), dtype=torch.uint8, device=lin8.device) if want_argmax else None
+    _launch("vfa_scale_view_max_f32", _lib.ptr(lin8), _lib.ptr(lin16), _lib.ptr(lin32), _lib.ptr(b8), _lib.ptr(b16), _lib.ptr(b32),
+            _lib.ptr(out), _lib.ptr(argmax), n, M, N, _lib.current_stream_handle(), tag=(n, M, N))
+    return out, argmax
+
+
+def scale_view_max_backward(grad, lin8, lin16, lin32, b8, b16, b32, argmax, want_bias=(True, True, True)):
+    """Backward of ``scale_view_max``: -> (grad_lin8, grad_lin16, grad_lin32 (n,M,N) dense, grad_b8, grad_b16, grad_b32 (N) or None).
+    Each element's gradient goes to its winning view only, through that view's ReLU masks (``vfa_scale_view_max_backward_f32``, no
+    float atomics).  The bias gradients are ``column_sum``s of the dense rows (a fixed order): bit-reproducible on every run."""
+    _lib.require_device(grad, lin8, lin16, lin32, b8, b16, b32, argmax)
+    n, M, N = lin8.shape
+    if tuple(argmax.shape) != (M, N) or argmax.dtype != torch.uint8:
+        raise ValueError(f"scale_view_max_backward: argmax must be uint8 ({M}, {N}), got {tuple(argmax.shape)} {argmax.dtype}")
+    grad, lin8, lin16, lin32, argmax = _f32c(grad), _f32c(lin8), _f32c(lin16), _f32c(lin32), argmax.contiguous()
+    b8, b16, b32 = (None if b is None else _f32c(b) for b in (b8, b16, b32))
+    glins = [torch.empty((n, M, N), dtype=torch.float32, device=lin8.device) for _ in range(3)]
+    _launch("vfa_scale_view_max_backward_f32", _lib.ptr(grad), _lib.ptr(lin8), _lib.ptr(lin16), _lib.ptr(lin32), _lib.ptr(b8),
+            _lib.ptr(b16), _lib.ptr(b32), _lib.ptr(argmax), *(_lib.ptr(g) for g in glins), None, None, None, n, M, N,
+            _lib.current_stream_handle(), tag=(n, M, N))
+    gbias = []
+    for g, b, want in zip(glins, (b8, b16, b32), want_bias):
+        gbias.append(column_sum(g.view(n * M, N)) if (b is not None and want) else None)
+    return (*glins, *gbias)
+
+
 def collapse_relu_sum(vox, weight, bias, out=None, accumulate=False, terms=0, reserved_cus=0):
     """out (M,N) (+)= sum_v relu(vox[v] @ weight.T + bias) in one bf16-split MFMA kernel (K = N = 256 only; reference
     vfa_op.py:121-124 + vfanet.py:82).  Raises ``VFAHipError`` (VFA_ERR_UNSUPPORTED) for other shapes."""

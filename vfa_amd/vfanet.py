@@ -8,6 +8,9 @@ per-camera computation of the reference.
 
 Multi-GPU (``distributed=True``): each rank runs backbone + laterals + projection for ITS cameras
 (``camera_shard``) and the partial BEV maps are summed with one RCCL all-reduce; heads run replicated.
+
+``view_reduce="max"`` fuses the cameras by an elementwise maximum instead of the reference's sum (``aggregate_views``; DESIGN.md
+4.9).  It is a plain attribute, not a buffer: the ``state_dict`` keys stay the reference's.
 """
 import glob
 import os
@@ -18,7 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops, vfa_op
-from .aggregate import aggregate_views, camera_shard
+from .aggregate import aggregate_views, camera_shard, check_view_reduce
 from .vfa_op import VFA
 
 # Producer fusion, inference on the fused frame path: the GroupNorm affine + ReLU of the lateral branch
@@ -125,11 +128,12 @@ def _head(cout):
 
 class VFANet(nn.Module):
     def __init__(self, args, base="resnet18", grid_height=160, cube_size=(25, 25, 32), angle_range=360, mode="3D",
-                 pretrained=False):
+                 pretrained=False, view_reduce="sum"):
         super().__init__()
         assert base in _DEPTHS, f"Unrecognized model, expect `resnet18` or `resnet34`, got {base}."
         assert mode in ("2D", "3D"), f"mode error, expect `2D` or `3D`, got{mode}"
         self.mode = mode
+        self.view_reduce = check_view_reduce(view_reduce)
         self.base = _Trunk(_DEPTHS[base])
         if pretrained:
             load_pretrained_trunk(self.base, base)
@@ -176,20 +180,21 @@ class VFANet(nn.Module):
             idx = torch.tensor(mine, dtype=torch.long, device=images.device)
             images, calibs = images[idx], calibs[idx]
         mods3 = [self.vfa8, self.vfa16, self.vfa32]
-        if (FUSE_PRODUCER and not torch.is_grad_enabled() and images.is_cuda and images.shape[0]
+        if (FUSE_PRODUCER and self.view_reduce == "sum" and not torch.is_grad_enabled() and images.is_cuda and images.shape[0]
                 and (vfa_op.fused_frame_ok(mods3, images.shape[0]) or vfa_op.pipe_frame_ok(mods3, images.shape[0]))):
             return aggregate_views(self.vfa8, self.vfa16, self.vfa32, None, None, None, calibs, grid, (-1, 0.95),
                                    distributed=distributed, integrals=self.lateral_integrals(images))
         lat8, lat16, lat32 = self.laterals(images) if images.shape[0] else (images.new_zeros(0, 256, 1, 1),) * 3
         return aggregate_views(self.vfa8, self.vfa16, self.vfa32, lat8, lat16, lat32, calibs, grid, (-1, 0.95),
-                               distributed=distributed)
+                               distributed=distributed, view_reduce=self.view_reduce)
 
     def _ortho_frames(self, images, calibs, grid, distributed):
         B, N = images.shape[:2]
         if calibs.dim() == 4 and tuple(calibs.shape[:2]) != (B, N) or calibs.dim() == 3 and calibs.shape[0] != N:
             raise ValueError(f"VFANet: images {tuple(images.shape)} need calibs ({N},3,4) or ({B},{N},3,4), got {tuple(calibs.shape)}")
         mods3 = [self.vfa8, self.vfa16, self.vfa32]
-        if B == 0 or distributed or calibs.dim() == 4 or torch.is_grad_enabled() or not (images.is_cuda and vfa_op.pipe_frames_ok(mods3, N)):
+        if (B == 0 or distributed or calibs.dim() == 4 or torch.is_grad_enabled() or self.view_reduce != "sum"
+                or not (images.is_cuda and vfa_op.pipe_frames_ok(mods3, N))):
             outs = [self.ortho_features(images[b], calibs[b] if calibs.dim() == 4 else calibs, grid, distributed) for b in range(B)]
             return torch.cat(outs, 0) if outs else images.new_zeros(0, 256, grid.shape[-3], grid.shape[-2])
         flat = images.reshape(B * N, *images.shape[2:])
@@ -218,7 +223,7 @@ class VFANet(nn.Module):
             for cam in range(images.shape[0]):
                 one = [l[cam:cam + 1] for l in lats]
                 part = aggregate_views(self.vfa8, self.vfa16, self.vfa32, *one, calibs[cam:cam + 1], grid)
-                fused = fused + part
+                fused = torch.maximum(fused, part) if (self.view_reduce == "max" and cam) else fused + part
                 fig, axes = plt.subplots(1, 5, figsize=(15, 3))
                 for ax, t, title in zip(axes, one + [part, fused], ("feat8", "feat16", "feat32", "ortho", "fused ortho")):
                     ax.imshow(torch.norm(t, dim=1)[0].cpu().numpy())
