@@ -157,6 +157,50 @@ int vfa_lateral_convs_f32(int n_maps, const float *const *feats, const float *co
                           float *const *scales, float *const *shifts, void *const *workspaces, const size_t *workspace_bytes, int n_views,
                           const int *Ks, const int *feat_hw, void *stream);
 
+/* Training through the producer: the same three launches as vfa_lateral_convs_f32 -- y, scale and shift bit for
+ * bit that call's --, plus the GroupNorm statistics the backward needs: means[s], rstds[s] (n_views, 16) DOUBLE, the mean and
+ * 1 / sqrt(var + eps) of each (view, group) (biased variance) exactly as the scale and shift were formed from them.  Both arrays and
+ * every entry required.  workspaces: vfa_lateral_conv_workspace_bytes, as above.
+ *   replaces the forward of vfa/model/vfanet.py:37-42, 72-74 under autograd */
+int vfa_lateral_convs_train_f32(int n_maps, const float *const *feats, const float *const *weights, const float *const *biases,
+                                const float *const *gammas, const float *const *betas, const float *eps, float *const *outs_hwc,
+                                float *const *scales, float *const *shifts, double *const *means, double *const *rstds,
+                                void *const *workspaces, const size_t *workspace_bytes, int n_views, const int *Ks, const int *feat_hw,
+                                void *stream);
+/* The backward of the producer, from d integral straight to the gradients of the trunk map and of the branch's parameters, in two
+ * calls per frame (HOST arrays of n_maps <= 3 entries, as vfa_lateral_convs_f32; C = 256, 16 groups, K a multiple of 32 and <= 1024):
+ *
+ * vfa_lateral_scan_backward_f32: grad_integrals[s] (n_views, H_s + 2, W_s + 2, 256) channels-last, 16-byte aligned (only the
+ *   interior is read: the border carries no gradient) -> dzs_hwc[s] (n_views, H_s, W_s, 256) = the reverse cumsums along H, then W
+ *   (vfa_integral_image_backward_f32's sequence, bit for bit, channels-last) times the ReLU mask [y * scale + shift > 0] recomputed
+ *   in the forward row scan's two fp32 operations from ys_hwc, scales, shifts (vfa_lateral_convs_train_f32's outputs).  Per (view,
+ *   channel) the sums S1 = sum dz and S2 = sum dz (y - mean) in double, added in a fixed order, give
+ *     grad_betas[s] = sum_n S1,  grad_gammas[s] = sum_n rstd S2,  grad_biases[s] = d conv bias (the exact sum of d y below, in double)
+ *   (each array NULL, or entries NULL, to skip), and the workspace keeps the coefficients of
+ *     d y = (rstd gamma_c) dz - rstd^2 B_g (y - mean) - rstd A_g,  A_g = mean_g(gamma S1) / P,  B_g = rstd mean_g(gamma S2) / P
+ *   for the second call.
+ * vfa_lateral_conv_backward_f32: forms d y on the fly from dzs_hwc, ys_hwc, means and the workspace the scan call filled, then
+ *     grad_feats[s]   (n_views, K_s, H_s, W_s) NCHW = W^T d y                 (the trunk map's gradient)
+ *     grad_weights[s] (256, K_s)                    = sum over views and pixels of d y f^T
+ *   six bf16 MFMA products of a three-piece split of both operands with fp32 accumulation (sgemm class); grad_weights from
+ *   per-workgroup partials added in a fixed order.  Either array, or any entry, NULL: that product is not run (a frozen trunk pays no
+ *   d f product).  feats[s] (n_views, K_s, H_s, W_s) and weights[s] (256, K_s) are the forward's inputs.
+ * workspaces[s]: vfa_lateral_backward_workspace_bytes(n_views, K_s, H_s, W_s) bytes, 16-byte aligned, the SAME buffer for both calls of
+ * a frame.  ys_hwc and dzs_hwc 16-byte aligned too (vfa_lateral_conv_backward_f32 reads them as float4).
+ * No float atomics: both calls give the same bits on every run.  Errors: VFA_ERR_BAD_ARGUMENT (NULL required pointer, short workspace,
+ * n_maps outside 1..3), VFA_ERR_UNSUPPORTED (K, alignment or size outside the limits above).
+ *   replace the autograd of vfa/model/vfanet.py:37-42, 72-74 and vfa_op.py:172-173 under vfa/trainer.py:41 */
+size_t vfa_lateral_backward_workspace_bytes(int n_views, int K, int Hf, int Wf);
+int vfa_lateral_scan_backward_f32(int n_maps, const float *const *grad_integrals, const float *const *ys_hwc, const float *const *scales,
+                                  const float *const *shifts, const double *const *means, const double *const *rstds,
+                                  const float *const *gammas, float *const *dzs_hwc, float *const *grad_biases, float *const *grad_gammas,
+                                  float *const *grad_betas, void *const *workspaces, const size_t *workspace_bytes, int n_views,
+                                  const int *Ks, const int *feat_hw, void *stream);
+int vfa_lateral_conv_backward_f32(int n_maps, const float *const *dzs_hwc, const float *const *ys_hwc, const double *const *means,
+                                  const float *const *feats, const float *const *weights, float *const *grad_feats,
+                                  float *const *grad_weights, void *const *workspaces, const size_t *workspace_bytes, int n_views,
+                                  const int *Ks, const int *feat_hw, void *stream);
+
 /* Cube corners -> world units -> 3x4 projection -> normalise/clamp -> 2-D bounding box, area and
  * visibility of every (view, layer, cell).                      replaces vfa_op.py:64-88, 104-106
  * and vfa/utils.py:50-59 (project).

@@ -334,8 +334,9 @@ def aggregate_views(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange
     only; ``distributed="reduce_scatter"``: every rank gets its band of BEV rows plus ``halo`` rows of its neighbours (default
     ``HEAD_HALO_ROWS`` = 7: what `fuse` + the dilation-4 heads read; see ``reduce_scatter_ortho`` for what is NOT band-local) and the
     call returns ``(band (1,C,rows,W), (row0, row1), (top, bottom))``.
-    ``integrals``: the three integral-image batches instead of the lateral maps (producer fusion, inference on the fused frame
-    path only; ``lat*`` may then be None).
+    ``integrals``: the three integral-image batches instead of the lateral maps (producer fusion; ``lat*`` may then be None).  With
+    gradients they go through the fused training node (``vfa_op.fused_train_ok``), whose backward hands the channels-last d integral
+    to the producer's node (``VFANet.lateral_integrals``); sum mode only.
     ``frames=B``: a batch of B frames -> (B,C,L,W).  lat* (or ``integrals``) hold B*n maps, frame-major; calibs is ONE rig (n,3,4)
     for every frame, or (B,n,3,4) a rig per frame.  One rig and inference: ONE launch of the pipelined kernel for the whole batch
     (``vfa_op.pipe_frames``); anything else -- a rig per frame, gradients, distributed reductions -- runs frame by frame and stacks.
@@ -366,9 +367,15 @@ def aggregate_views(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange
             ortho, argmax = _ScaleViewMax.apply(*lins, vfa8.collapse.bias, vfa16.collapse.bias, vfa32.collapse.bias)
         else:  # a rank without cameras: zeros, below every camera's map
             ortho = torch.zeros((length * width, vfa8.collapse.out_features), dtype=torch.float32, device=grid.device)
+    elif integrals is not None and n > 0 and vfa_op.fused_train_ok(mods3, n, tuple(integrals), (calibs, grid)):
+        # training on the producer's integral images (``VFANet.lateral_integrals`` / ``vfa_op._LateralIntegrals``): the fused frame node
+        # hands the channels-last d integral back to the producer's node
+        ortho = vfa_op.fused_frame_train(mods3, None, calibs, grid, crange, reserved_cus=reserved, integrals=integrals)
     elif integrals is not None:
-        assert n > 0 and not torch.is_grad_enabled() and (vfa_op.pipe_frame_ok(mods3, n) or vfa_op.fused_frame_ok(mods3, n)), \
-            "integral-image inputs need a per-frame inference path"
+        assert n > 0 and (vfa_op.pipe_frame_ok(mods3, n) or vfa_op.fused_frame_ok(mods3, n)), \
+            "integral-image inputs need a per-frame path"
+        assert not (torch.is_grad_enabled() and any(i.requires_grad for i in integrals)), \
+            "integral-image inputs with gradients need the fused training node (fused_train_ok)"
         ortho = torch.empty((length * width, vfa8.collapse.out_features), dtype=torch.float32, device=grid.device)
         frame = vfa_op.pipe_frame if vfa_op.pipe_frame_ok(mods3, n) else vfa_op.fused_frame
         frame(mods3, None, calibs, grid, crange, out=ortho, reserved_cus=reserved, integrals=integrals)  # (an ops.IntegralImages keeps its feature statistics)

@@ -257,6 +257,7 @@ struct FinalArgs {
     int parts;                 // 32-pixel blocks, rounded up to whole workgroups
     double count;              // H * W * 16
     float eps;
+    double *mean, *rstd;       // (n_views, 16) or NULL: the group statistics themselves (training: vfa_lateral_convs_train_f32)
 };
 // one wave per (view, group): lane j adds the partial sums j, j + 64, ... (64 chains in flight: ONE chain of 452 dependent loads per
 // thread took 200 us on the bench frame, 16 chains per group 15), then a fixed butterfly (no atomics: the same bits on every run), then
@@ -282,6 +283,10 @@ __device__ __forceinline__ void lateral_stats(const FinalArgs &a)
     double var = s2 / a.count - mean * mean; // (biased, like nn.GroupNorm)
     if (var < 0.0) var = 0.0;
     const double rstd = 1.0 / sqrt(var + (double)a.eps);
+    if (a.mean && j == 0) {
+        a.mean[(size_t)v * kGroups + g] = mean;
+        a.rstd[(size_t)v * kGroups + g] = rstd;
+    }
     const float sc = (float)((double)a.gamma[c] * rstd);
     a.scale[(size_t)v * kCo + c] = sc;
     a.shift[(size_t)v * kCo + c] = (float)((double)a.beta[c] - mean * (double)a.gamma[c] * rstd);
@@ -332,10 +337,13 @@ static uint4 *lateral_frag_of(void *workspace, int n_views, int H, int W)
     return reinterpret_cast<uint4 *>(reinterpret_cast<unsigned char *>(workspace) + ((size_t)n_views * kGroups * parts * 2 * sizeof(double) + 255) / 256 * 256);
 }
 
-int vfa_lateral_convs_f32(int n_maps, const float *const *feats, const float *const *weights, const float *const *biases,
-                          const float *const *gammas, const float *const *betas, const float *eps, float *const *outs_hwc,
-                          float *const *scales, float *const *shifts, void *const *workspaces, const size_t *workspace_bytes, int n_views,
-                          const int *Ks, const int *feat_hw, void *stream)
+// vfa_lateral_convs_f32 and its training form vfa_lateral_convs_train_f32 (means / rstds: NULL, or arrays of n_maps (n_views, 16)
+// double buffers that receive the group statistics the stats kernel forms anyway): one implementation, the same kernels, the same bits.
+static int lateral_convs_launch(int n_maps, const float *const *feats, const float *const *weights, const float *const *biases,
+                                const float *const *gammas, const float *const *betas, const float *eps, float *const *outs_hwc,
+                                float *const *scales, float *const *shifts, double *const *means, double *const *rstds,
+                                void *const *workspaces, const size_t *workspace_bytes, int n_views, const int *Ks, const int *feat_hw,
+                                void *stream)
 {
     if (n_maps < 1 || n_maps > kMaxMaps || !feats || !weights || !biases || !gammas || !betas || !eps || !outs_hwc || !scales || !shifts ||
         !workspaces || !workspace_bytes || !Ks || !feat_hw)
@@ -374,6 +382,7 @@ int vfa_lateral_convs_f32(int n_maps, const float *const *feats, const float *co
         FinalArgs &f = fb.m[m];
         f.partial = a.partial; f.gamma = gammas[q]; f.beta = betas[q]; f.scale = scales[q]; f.shift = shifts[q];
         f.parts = a.blocks * pxw; f.count = (double)a.HW * (kCo / kGroups); f.eps = eps[q];
+        f.mean = means ? means[q] : nullptr; f.rstd = means ? rstds[q] : nullptr;
     }
     hipLaunchKernelGGL(lateral_split_weight_batched_kernel, dim3((unsigned)max_split, (unsigned)n_maps), dim3(256), 0, s, sb);
     int e = (int)hipGetLastError();
@@ -383,6 +392,28 @@ int vfa_lateral_convs_f32(int n_maps, const float *const *feats, const float *co
     if (e) return e;
     hipLaunchKernelGGL(lateral_stats_batched_kernel, dim3((unsigned)n_views * kGroups, (unsigned)n_maps), dim3(kWave), 0, s, fb);
     return (int)hipGetLastError();
+}
+
+int vfa_lateral_convs_f32(int n_maps, const float *const *feats, const float *const *weights, const float *const *biases,
+                          const float *const *gammas, const float *const *betas, const float *eps, float *const *outs_hwc,
+                          float *const *scales, float *const *shifts, void *const *workspaces, const size_t *workspace_bytes, int n_views,
+                          const int *Ks, const int *feat_hw, void *stream)
+{
+    return lateral_convs_launch(n_maps, feats, weights, biases, gammas, betas, eps, outs_hwc, scales, shifts, nullptr, nullptr, workspaces,
+                                workspace_bytes, n_views, Ks, feat_hw, stream);
+}
+
+int vfa_lateral_convs_train_f32(int n_maps, const float *const *feats, const float *const *weights, const float *const *biases,
+                                const float *const *gammas, const float *const *betas, const float *eps, float *const *outs_hwc,
+                                float *const *scales, float *const *shifts, double *const *means, double *const *rstds,
+                                void *const *workspaces, const size_t *workspace_bytes, int n_views, const int *Ks, const int *feat_hw,
+                                void *stream)
+{
+    if (!means || !rstds || n_maps < 1 || n_maps > kMaxMaps) return VFA_ERR_BAD_ARGUMENT;
+    for (int m = 0; m < n_maps; ++m)
+        if (!means[m] || !rstds[m]) return VFA_ERR_BAD_ARGUMENT;
+    return lateral_convs_launch(n_maps, feats, weights, biases, gammas, betas, eps, outs_hwc, scales, shifts, means, rstds, workspaces,
+                                workspace_bytes, n_views, Ks, feat_hw, stream);
 }
 
 int vfa_lateral_conv_f32(const float *feat, const float *weight, const float *bias, const float *gamma, const float *beta, float eps,
@@ -415,6 +446,7 @@ int vfa_lateral_conv_f32(const float *feat, const float *weight, const float *bi
     FinalArgs f;
     f.partial = a.partial; f.gamma = gamma; f.beta = beta; f.scale = scale; f.shift = shift;
     f.parts = a.blocks * pxw; f.count = (double)a.HW * (kCo / kGroups); f.eps = eps;
+    f.mean = nullptr; f.rstd = nullptr;
     hipLaunchKernelGGL(lateral_stats_kernel, dim3((unsigned)n_views * kGroups), dim3(kWave), 0, s, f);
     return (int)hipGetLastError();
 }

@@ -220,6 +220,92 @@ def lateral_convs(branches):
     return list(zip(outs, scales, shifts))
 
 
+def lateral_convs_train(branches):
+    """``lateral_convs`` for training (``vfa_lateral_convs_train_f32``): the same y, scale, shift bit for bit, plus the GroupNorm
+    statistics the backward needs -> [(y, scale, shift, mean, rstd), ...] with mean / rstd (n,16) float64 per (view, group)."""
+    dev = branches[0][0].device
+    n = branches[0][0].shape[0]
+    feats, weights, biases, gammas, betas, epss, outs, scales, shifts, means, rstds, wss, Ks, hws = ([] for _ in range(14))
+    for feat, weight, bias, gamma, beta, eps in branches:
+        _lib.require_device(feat, weight, bias, gamma, beta)
+        feat, weight = _f32c(feat), _f32c(weight.reshape(weight.shape[0], -1))
+        assert feat.shape[0] == n and tuple(weight.shape) == (256, feat.shape[1])
+        _, K, h, w = feat.shape
+        feats.append(feat), weights.append(weight), biases.append(_f32c(bias)), gammas.append(_f32c(gamma)), betas.append(_f32c(beta))
+        epss.append(float(eps)), Ks.append(int(K)), hws.extend((int(h), int(w)))
+        outs.append(torch.empty((n, h, w, 256), dtype=torch.float32, device=dev))
+        scales.append(torch.empty((n, 256), dtype=torch.float32, device=dev))
+        shifts.append(torch.empty((n, 256), dtype=torch.float32, device=dev))
+        means.append(torch.empty((n, 16), dtype=torch.float64, device=dev))
+        rstds.append(torch.empty((n, 16), dtype=torch.float64, device=dev))
+        need = _lib.lib().vfa_lateral_conv_workspace_bytes(n, h, w)
+        key = (dev.index, _lib.current_stream(dev).cuda_stream, need, len(wss))
+        ws = _lateral_ws.get(key)
+        if ws is None:
+            ws = _lateral_ws[key] = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+        wss.append(ws)
+    m = len(branches)
+    _launch("vfa_lateral_convs_train_f32", m, _lib.ptr_array(feats), _lib.ptr_array(weights), _lib.ptr_array(biases),
+            _lib.ptr_array(gammas), _lib.ptr_array(betas), (ctypes.c_float * m)(*epss), _lib.ptr_array(outs), _lib.ptr_array(scales),
+            _lib.ptr_array(shifts), _lib.ptr_array(means), _lib.ptr_array(rstds), _lib.ptr_array(wss),
+            (ctypes.c_size_t * m)(*[w.numel() for w in wss]), n, _lib.int_array(Ks), _lib.int_array(hws), _lib.current_stream_handle(),
+            tag=(n, tuple(Ks), tuple(hws)))
+    return list(zip(outs, scales, shifts, means, rstds))
+
+
+def lateral_backward_workspace_bytes(n_views, K, h, w):
+    """Bytes of the workspace one map's two backward calls share (``vfa_lateral_backward_workspace_bytes``)."""
+    return int(_lib.lib().vfa_lateral_backward_workspace_bytes(int(n_views), int(K), int(h), int(w)))
+
+
+def lateral_scan_backward(grad_integrals, ys, scales, shifts, means, rstds, gammas, Ks, want=(True, True, True)):
+    """First half of the producer's backward (``vfa_lateral_scan_backward_f32``), all maps in one launch sequence: d integral
+    (n,h+2,w+2,256) per map -> (dzs (n,h,w,256) channels-last, [d bias], [d gamma], [d beta], workspaces).  ``want`` = (bias, gamma,
+    beta): the parameter gradients to write (None where not wanted).  The workspaces carry the d y coefficients to
+    ``lateral_conv_backward``."""
+    m = len(grad_integrals)
+    dev = grad_integrals[0].device
+    n = grad_integrals[0].shape[0]
+    grad_integrals = [_f32c(g) for g in grad_integrals]
+    _lib.require_device(*grad_integrals, *ys, *scales, *shifts, *means, *rstds, *gammas)
+    hws = [v for g in grad_integrals for v in (g.shape[1] - 2, g.shape[2] - 2)]
+    dzs = [torch.empty((n, g.shape[1] - 2, g.shape[2] - 2, 256), dtype=torch.float32, device=dev) for g in grad_integrals]
+    wss = [torch.empty(max(lateral_backward_workspace_bytes(n, K, hws[2 * i], hws[2 * i + 1]), 8), dtype=torch.uint8, device=dev)
+           for i, K in enumerate(Ks)]
+    outs = [[torch.empty(256, dtype=torch.float32, device=dev) if w else None for _ in range(m)] for w in want]
+    _launch("vfa_lateral_scan_backward_f32", m, _lib.ptr_array(grad_integrals), _lib.ptr_array(ys), _lib.ptr_array(scales),
+            _lib.ptr_array(shifts), _lib.ptr_array(means), _lib.ptr_array(rstds), _lib.ptr_array([_f32c(g) for g in gammas]),
+            _lib.ptr_array(dzs), _lib.ptr_array(outs[0]), _lib.ptr_array(outs[1]), _lib.ptr_array(outs[2]), _lib.ptr_array(wss),
+            (ctypes.c_size_t * m)(*[w.numel() for w in wss]), n, _lib.int_array(Ks), _lib.int_array(hws), _lib.current_stream_handle(),
+            tag=(n, tuple(Ks), tuple(hws), tuple(bool(w) for w in want)))
+    return dzs, outs[0], outs[1], outs[2], wss
+
+
+def lateral_conv_backward(dzs, ys, means, feats, weights, workspaces, want_feat=True, want_weight=True):
+    """Second half (``vfa_lateral_conv_backward_f32``): d y formed on the fly, then per map d feat (n,K,h,w) NCHW and d weight
+    (256,K), one launch sequence for all maps.  ``want_feat`` / ``want_weight``: a bool or one bool per map; a product that is not
+    wanted is not run.  Returns (d feats, d weights), None where not wanted."""
+    m = len(dzs)
+    n = dzs[0].shape[0]
+    dev = dzs[0].device
+    feats = [_f32c(f) for f in feats]
+    weights = [_f32c(w.reshape(w.shape[0], -1)) for w in weights]
+    _lib.require_device(*dzs, *ys, *means, *feats, *weights)
+    wf = [bool(want_feat)] * m if isinstance(want_feat, bool) else [bool(w) for w in want_feat]
+    ww = [bool(want_weight)] * m if isinstance(want_weight, bool) else [bool(w) for w in want_weight]
+    Ks = [int(f.shape[1]) for f in feats]
+    hws = [int(v) for f in feats for v in f.shape[2:]]
+    g_f = [torch.empty_like(f) if w else None for f, w in zip(feats, wf)]
+    g_w = [torch.empty((256, K), dtype=torch.float32, device=dev) if w else None for K, w in zip(Ks, ww)]
+    if not (any(wf) or any(ww)):
+        return g_f, g_w
+    _launch("vfa_lateral_conv_backward_f32", m, _lib.ptr_array(dzs), _lib.ptr_array(ys), _lib.ptr_array(means), _lib.ptr_array(feats),
+            _lib.ptr_array(weights), _lib.ptr_array(g_f), _lib.ptr_array(g_w), _lib.ptr_array(workspaces),
+            (ctypes.c_size_t * m)(*[w.numel() for w in workspaces]), n, _lib.int_array(Ks), _lib.int_array(hws),
+            _lib.current_stream_handle(), tag=(n, tuple(Ks), tuple(hws), tuple(wf), tuple(ww)))
+    return g_f, g_w
+
+
 def box_params(calibs, grid_flat, z_layers, corner_off, conv_kind, image_wh, feat_hw, crange=(-1, 0.95)):
     """-> box (n,nl,cells,4), area (n,nl,cells), visible (n,nl,cells) uint8 (reference vfa_op.py:64-106)."""
     _lib.require_device(calibs, grid_flat, z_layers, corner_off)

@@ -547,12 +547,16 @@ class _FusedFrameTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, calibs, grid, crange, meta, reserved_cus, *tensors):
-        mods = meta
+        mods, from_integrals = meta
         ns = len(mods)
         lats, weights, biases = tensors[:ns], tensors[ns:2 * ns], tensors[2 * ns:3 * ns]
         n = calibs.shape[0]
         with torch.no_grad():
-            integrals = ops.integral_images([l.detach() for l in lats])  # kept: the backward pools from them again
+            if from_integrals:  # the producer's integral images (``_LateralIntegrals``) and their feature statistics
+                integrals = ops.IntegralImages(l.detach() for l in lats)
+                integrals.absmax = list(tensors[3 * ns:4 * ns])
+            else:
+                integrals = ops.integral_images([l.detach() for l in lats])  # kept: the backward pools from them again
             piped = pipe_frame_ok(mods, n)
             frame = pipe_frame if piped else fused_frame
             out = frame(mods, None, calibs, grid, crange, reserved_cus=reserved_cus, integrals=integrals)
@@ -560,12 +564,12 @@ class _FusedFrameTrain(torch.autograd.Function):
         # mask is the forward's bit for bit)
         f16 = (COLLAPSE_TERMS if piped else _fused_terms()) in (0, 2)
         ctx.save_for_backward(calibs, grid, *integrals, *weights, *biases, *(integrals.absmax if f16 else ()))
-        ctx.meta = (mods, tuple(float(c) for c in crange), piped, f16)
+        ctx.meta = (mods, tuple(float(c) for c in crange), piped, f16, from_integrals)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        mods, crange, piped, f16 = ctx.meta
+        mods, crange, piped, f16, from_integrals = ctx.meta
         ns = len(mods)
         calibs, grid = ctx.saved_tensors[:2]
         integrals = ctx.saved_tensors[2:2 + ns]
@@ -642,19 +646,95 @@ class _FusedFrameTrain(torch.autograd.Function):
                                                                  want_grid=False, accumulate=True)
                         del g_vox
                     del vox, g_lin
-                g_lats.append(ops.integral_image_backward(g_int) if need_lat else None)
+                # (integral-image inputs: the channels-last d integral itself goes to the producer's node)
+                g_lats.append((g_int if from_integrals else ops.integral_image_backward(g_int)) if need_lat else None)
                 g_ws.append(g_w_lm.view(C, nl, C).permute(0, 2, 1).reshape(C, C * nl) if need_w else None)
                 g_bs.append(g_b)
         d_calibs = g_cal.view(calibs.shape).to(calibs.dtype) if need_cal else None
         d_grid = g_grid.view(grid.shape).to(grid.dtype) if need_grid else None
-        return (d_calibs, d_grid, None, None, None, *g_lats, *g_ws, *g_bs)
+        return (d_calibs, d_grid, None, None, None, *g_lats, *g_ws, *g_bs, *((None,) * (ns if from_integrals else 0)))
 
 
-def fused_frame_train(mods, features, calibs, grid, crange=(-1, 0.95), reserved_cus=0):
+class _LateralIntegrals(torch.autograd.Function):
+    """The producer as ONE autograd node (reference vfanet.py:37-42, 72-74 + vfa_op.py:172-173 under trainer.py:41): trunk maps
+    (n,K_s,h_s,w_s) and the conv / GroupNorm parameters of each scale -> the zero-bordered channels-last integral images of
+    relu(GroupNorm16(conv1x1(f))), plus their feature statistics (``absmax``, int32, non-differentiable) for the frame kernels.
+
+    forward: ``vfa_lateral_convs_train_f32`` (the inference kernels; y, scale, shift bit for bit ``lateral_convs``, plus the float64
+    group mean / rstd) and ``vfa_integral_images_hwc_f32`` with the affine + ReLU in its row scan: no lateral map is written.  Kept
+    for the backward: the trunk maps (references), y, scale / shift and mean / rstd.
+    backward: ``vfa_lateral_scan_backward_f32`` (reverse scans, the forward's ReLU mask, the GroupNorm sums in double: d gamma,
+    d beta, d conv bias) and ``vfa_lateral_conv_backward_f32`` (d trunk map and d conv weight, d y formed on the fly).  A product
+    nobody asked for is not run.  No float atomics: the same bits on every run."""
+
+    @staticmethod
+    def forward(ctx, eps, *tensors):
+        ns = len(eps)
+        feats, weights, biases, gammas, betas = (tensors[i * ns:(i + 1) * ns] for i in range(5))
+        with torch.no_grad():
+            parts = ops.lateral_convs_train([(f.detach(), w.detach(), b.detach(), g.detach(), be.detach(), e)
+                                             for f, w, b, g, be, e in zip(feats, weights, biases, gammas, betas, eps)])
+            ys, scales, shifts, means, rstds = (list(t) for t in zip(*parts))
+            integrals = ops.integral_images(ys, scales, shifts, channels_last=True)
+        absmax = list(integrals.absmax)
+        ctx.mark_non_differentiable(*absmax)
+        ctx.save_for_backward(*feats, *weights, *gammas, *ys, *scales, *shifts, *means, *rstds)
+        ctx.ns = ns
+        return (*integrals, *absmax)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        ns = ctx.ns
+        saved = ctx.saved_tensors
+        feats, weights, gammas, ys, scales, shifts, means, rstds = (saved[i * ns:(i + 1) * ns] for i in range(8))
+        need = ctx.needs_input_grad[1:]
+        n_f, n_w, n_b, n_g, n_be = (need[i * ns:(i + 1) * ns] for i in range(5))
+        if not any(need):
+            return (None,) * (1 + 5 * ns)
+        g_int = [torch.zeros((y.shape[0], y.shape[1] + 2, y.shape[2] + 2, y.shape[3]), dtype=torch.float32, device=y.device)
+                 if g is None else g for g, y in zip(grads[:ns], ys)]
+        with torch.no_grad():
+            dzs, g_b, g_g, g_be, wss = ops.lateral_scan_backward(g_int, ys, scales, shifts, means, rstds, gammas,
+                                                                 [f.shape[1] for f in feats], want=(any(n_b), any(n_g), any(n_be)))
+            g_f, g_w = ops.lateral_conv_backward(dzs, ys, means, feats, weights, wss, want_feat=n_f, want_weight=n_w)
+        g_w = [None if g is None else g.view_as(w) for g, w in zip(g_w, weights)]
+
+        def keep(gs, wants):
+            return [g if w else None for g, w in zip(gs, wants)]
+        return (None, *keep(g_f, n_f), *keep(g_w, n_w), *keep(g_b, n_b), *keep(g_g, n_g), *keep(g_be, n_be))
+
+
+def lateral_integrals_train(feats, convs, norms):
+    """Differentiable producer: the trunk maps and the lateral conv / GroupNorm modules of each scale -> an ``ops.IntegralImages``
+    (channels-last integral images of relu(norm(conv(f))), with ``absmax``) through ``_LateralIntegrals``."""
+    ns = len(feats)
+    tensors = list(feats) + [c.weight for c in convs] + [c.bias for c in convs] + [g.weight for g in norms] + [g.bias for g in norms]
+    outs = _LateralIntegrals.apply(tuple(float(g.eps) for g in norms), *tensors)
+    integrals = ops.IntegralImages(outs[:ns])
+    integrals.absmax = list(outs[ns:])
+    return integrals
+
+
+def fused_frame_train(mods, features, calibs, grid, crange=(-1, 0.95), reserved_cus=0, integrals=None):
     """``sum_scale sum_view relu(collapse_scale(vox))`` as (L*W, 256) WITH autograd: fused forward, recomputing backward
-    (``_FusedFrameTrain``).  Needs ``_frame_kernels_cover`` and, on single-layer grids, nothing else; see ``FUSED_TRAIN``."""
-    tensors = list(features) + [m.collapse.weight for m in mods] + [m.collapse.bias for m in mods]
-    return _FusedFrameTrain.apply(calibs, grid, tuple(crange), tuple(mods), reserved_cus, *tensors)
+    (``_FusedFrameTrain``).  Needs ``_frame_kernels_cover`` and, on single-layer grids, nothing else; see ``FUSED_TRAIN``.
+    ``integrals``: the zero-bordered channels-last integral images instead of ``features`` (an ``ops.IntegralImages`` with its
+    ``absmax``, as ``lateral_integrals`` returns them; differentiable through ``_LateralIntegrals``): the node's gradient for them is
+    the channels-last d integral, no NCHW d lateral is formed."""
+    from_integrals = integrals is not None
+    maps = list(integrals) if from_integrals else list(features)
+    tensors = maps + [m.collapse.weight for m in mods] + [m.collapse.bias for m in mods]
+    if from_integrals:
+        absmax = getattr(integrals, "absmax", None) or [ops.integral_absmax(i.detach()) for i in integrals]
+        tensors += list(absmax)
+    return _FusedFrameTrain.apply(calibs, grid, tuple(crange), (tuple(mods), from_integrals), reserved_cus, *tensors)
+
+
+def producer_train_ok(mods, n_views):
+    """The fused training node can take the producer's integral images for this module set / camera count (the gates of
+    ``fused_train_ok`` that do not look at ``requires_grad``)."""
+    return (FUSED_TRAIN and _frame_kernels_cover(mods, n_views)
+            and (PIPE or (mods[0].num_grid_layer == 1 and FUSED_POOL)))
 
 
 def fused_train_ok(mods, n_views, features, geometry=()):

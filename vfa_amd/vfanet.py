@@ -27,6 +27,10 @@ from .vfa_op import VFA
 # Producer fusion, inference on the fused frame path: the GroupNorm affine + ReLU of the lateral branch
 # is applied inside the integral-image row scan (`vfa_affine_relu_integral_image_f32`); the lateral maps are never written.
 FUSE_PRODUCER = os.environ.get("VFA_AMD_FUSE_PRODUCER", "1") == "1"
+# ... and in TRAINING (off by default): with gradients, sum mode and a module set the fused frame kernels cover, the producer runs as
+# one autograd node (``vfa_op._LateralIntegrals``: HIP forward and backward kernels, no NCHW lateral map or d lateral) feeding the
+# fused frame node with integral images.  Otherwise training runs ``laterals()`` (MIOpen conv, torch GroupNorm and ReLU).
+FUSE_PRODUCER_TRAIN = os.environ.get("VFA_AMD_FUSE_PRODUCER_TRAIN", "0") == "1"
 
 # ``pretrained=True`` (the default of the reference's train.py:90): the reference downloads the torchvision ImageNet
 # checkpoint (resnet.py:155-159, 170-172).  There is no network on the MI355X boxes, so the file is looked up locally.
@@ -163,8 +167,12 @@ class VFANet(nn.Module):
         materialising those maps (reference vfanet.py:72-74 + vfa_op.py:110, 172-173).  ONE hand-written kernel for the three
         1x1 convolutions (``ops.lateral_convs``: six bf16 MFMA products of a three-piece split, channels-last output, GroupNorm
         statistics in its epilogue) + a tiny statistics kernel; then one launch pair for the three integral images, whose row scan applies the
-        GroupNorm affine and the ReLU (``vfa_integral_images_hwc_f32``).  No NCHW lateral tensor exists."""
+        GroupNorm affine and the ReLU (``vfa_integral_images_hwc_f32``).  No NCHW lateral tensor exists.
+        With gradients enabled the same kernels run inside one autograd node (``vfa_op._LateralIntegrals``) whose backward goes from
+        d integral straight to the trunk maps and the lat* / bn* parameters on HIP kernels."""
         x = (images - self.mean.view(3, 1, 1)) / self.std.view(3, 1, 1)
+        if torch.is_grad_enabled():
+            return vfa_op.lateral_integrals_train(self.base(x), (self.lat8, self.lat16, self.lat32), (self.bn8, self.bn16, self.bn32))
         parts = ops.lateral_convs([(feat, conv.weight, conv.bias, gn.weight, gn.bias, gn.eps) for feat, conv, gn in
                                    zip(self.base(x), (self.lat8, self.lat16, self.lat32), (self.bn8, self.bn16, self.bn32))])
         return ops.integral_images([p[0] for p in parts], [p[1] for p in parts], [p[2] for p in parts], channels_last=True)
@@ -184,9 +192,20 @@ class VFANet(nn.Module):
                 and (vfa_op.fused_frame_ok(mods3, images.shape[0]) or vfa_op.pipe_frame_ok(mods3, images.shape[0]))):
             return aggregate_views(self.vfa8, self.vfa16, self.vfa32, None, None, None, calibs, grid, (-1, 0.95),
                                    distributed=distributed, integrals=self.lateral_integrals(images))
+        if self.producer_train_ok(images):
+            return aggregate_views(self.vfa8, self.vfa16, self.vfa32, None, None, None, calibs, grid, (-1, 0.95),
+                                   distributed=distributed, integrals=self.lateral_integrals(images))
         lat8, lat16, lat32 = self.laterals(images) if images.shape[0] else (images.new_zeros(0, 256, 1, 1),) * 3
         return aggregate_views(self.vfa8, self.vfa16, self.vfa32, lat8, lat16, lat32, calibs, grid, (-1, 0.95),
                                distributed=distributed, view_reduce=self.view_reduce)
+
+    def producer_train_ok(self, images):
+        """Training routes through the differentiable producer (``FUSE_PRODUCER_TRAIN``): gradients on, sum mode, a CUDA batch of
+        cameras with the lateral widths of the reference, and the fused frame kernels cover the modules."""
+        mods3 = [self.vfa8, self.vfa16, self.vfa32]
+        return (FUSE_PRODUCER_TRAIN and self.view_reduce == "sum" and torch.is_grad_enabled() and images.is_cuda
+                and images.shape[0] > 0 and all(c.out_channels == 256 for c in (self.lat8, self.lat16, self.lat32))
+                and vfa_op.producer_train_ok(mods3, images.shape[0]))
 
     def _ortho_frames(self, images, calibs, grid, distributed):
         B, N = images.shape[:2]
