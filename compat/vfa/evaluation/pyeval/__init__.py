@@ -1,0 +1,7 @@
+"""``vfa.evaluation.pyeval``: `evaluateAPAOS` is the alias module next to this file; every other module of the reference's
+``vfa/evaluation/pyeval`` directory (IoU.py, CLEAR_MOD_HUN.py, evaluateDetection.py, cuda_op/) still resolves to the checkout."""
+import os
+
+from ... import _reference_dirs
+
+__path__ = [os.path.dirname(os.path.abspath(__file__))] + _reference_dirs(os.path.join("evaluation", "pyeval"))

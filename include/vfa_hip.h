@@ -617,6 +617,47 @@ int vfa_bev_nms_f32(const float *heatmap, float *conf, int L, int W, void *strea
 /* vfa_bev_nms_batch_f32: the same for B maps (B, L, W) in one launch; the 5 x 5 window never crosses from one frame into the next. */
 int vfa_bev_nms_batch_f32(const float *heatmap, float *conf, int B, int L, int W, void *stream);
 
+/* ---- the AP/AOS metric: rotated-box 3D IoU and the best ground truth of every detection ---------------------------------------
+ *
+ * A box is 7 floats  x y z l w h alpha  (centre, footprint l x w rotated by alpha around z, height h).  ONE LANE computes the
+ * whole IoU3D of one pair (corners, 16 edge intersections, corner-inside tests, 24 candidate vertices, their ordering by the device
+ * code of vfa_sort_vertices_f32, shoelace, union, z overlap); the candidates stay in LDS, memory sees the boxes and the results.
+ * fp32, one operation per reference operation in the reference's order, no contraction; cosf / sinf are the device's, so the
+ * reference's numbers are met within a tolerance, not bit for bit.  No atomics: every call gives the same bits on every run.
+ *
+ * vfa_iou3d_f32: elementwise.  box1, box2 (count, 7); iou3d (count) out; iou_bev (count) out or NULL: the IoU of the footprints
+ * (the first result of IoUs2D).                              replaces vfa/evaluation/pyeval/IoU.py:6-225 for one pair per lane
+ *   - the z overlap  min(zmax) - max(zmin)  is NOT clamped, like the reference's: boxes apart in z whose footprints overlap give a
+ *     NEGATIVE IoU (above -1), which no positive threshold accepts;
+ *   - footprints that do not meet give exactly 0 (never NaN); a NaN in any field of either box gives NaN in iou3d (a NaN in z or h:
+ *     in iou3d only); boxes of zero area give 0 / 0 = NaN like the reference;
+ *   - count == 0 returns 0 and touches nothing; count < 0 or a NULL box1 / box2 / iou3d: VFA_ERR_BAD_ARGUMENT; more than
+ *     2^31 - 1 blocks of 64 pairs: VFA_ERR_UNSUPPORTED.
+ *
+ * vfa_iou3d_frames_f32: a whole evaluation set in one call.  det (n_det, 7) and gt (n_gt, 7), both sorted by frame; det_begin,
+ * gt_begin (n_frames + 1) int32 CSR offsets of the frames' rows; pair_begin (n_frames + 1) int64: offset of each frame's
+ * (P_f, G_f) IoU matrix (detection-major) in the packed output iou (n_pairs), n_pairs = pair_begin[n_frames] = sum P_f * G_f.
+ *                                                            replaces the loops of vfa/evaluation/pyeval/evaluateAPAOS.py:74-92
+ *   - iou != NULL: one lane per pair fills the matrices;
+ *   - best_idx (n_det) int32 and best_iou (n_det) != NULL: per detection the LOWEST-INDEX MAXIMUM of its row: best_idx =
+ *     frame-local index of that ground truth, best_iou its IoU; a NaN never wins; best_idx = -1 and best_iou = -1 when the frame
+ *     has no ground truth or every IoU of the row is NaN.  Detections outside [det_begin[0], det_begin[n_frames]) get -1 / -1.
+ *     16 lanes share a row and combine by value, then by lowest index: what a scan in index order keeps, whatever the order of
+ *     the combination;
+ *   - iou == NULL: no matrix is written or read (pair_begin may be NULL, n_pairs is ignored): the detection's lanes compute its
+ *     row themselves with the same device function on the same operands, so best_idx / best_iou have the bits of the matrix form;
+ *   - best_idx == NULL and best_iou == NULL: only the matrices.  One of the two NULL: VFA_ERR_BAD_ARGUMENT.
+ * Why one best match serves every threshold: the reference keeps pair j when  iou >= thresh and iou > max_iou  with max_iou
+ * starting at -1 (evaluateAPAOS.py:80-87); for any thresh > 0 that is "the first j that attains the row's maximum, if that maximum
+ * is >= thresh".  So the thresholds 0.75 / 0.5 / 0.25 share one argmax and differ in one comparison of best_iou (the host wrapper
+ * refuses thresholds <= 0, for which the equivalence does not hold).
+ * Limits and errors: negative counts, a NULL det / det_begin / gt_begin (or gt with n_gt > 0, or pair_begin with iou):
+ * VFA_ERR_BAD_ARGUMENT; n_frames == 0 or n_det == 0 returns 0.  Offsets that leave [0, n_det] / [0, n_gt] / [0, n_pairs) are not
+ * followed (such a frame's outputs are left unwritten, or -1): a wrong table cannot make the kernels read or write out of bounds. */
+int vfa_iou3d_f32(const float *box1, const float *box2, float *iou3d, float *iou_bev, long long count, void *stream);
+int vfa_iou3d_frames_f32(const float *det, const int *det_begin, const float *gt, const int *gt_begin, int n_frames, int n_det, int n_gt,
+                         const long long *pair_begin, long long n_pairs, float *iou, int *best_idx, float *best_iou, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

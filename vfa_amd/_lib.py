@@ -118,6 +118,8 @@ SIGNATURES = {
                                              _c_int, _c_int, _vp],
     "vfa_pipe_batch_balance_f32": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_size_t, _vp],
     "vfa_bev_nms_batch_f32": [_vp, _vp, _c_int, _c_int, _c_int, _vp],
+    "vfa_iou3d_f32": [_vp, _vp, _vp, _vp, _c_longlong, _vp],
+    "vfa_iou3d_frames_f32": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _c_longlong, _vp, _vp, _vp, _vp],
 }
 
 _lib = None

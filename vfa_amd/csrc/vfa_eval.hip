@@ -11,30 +11,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vfa_eval_sort.h"
 #include "vfa_hip.h"
 
 namespace {
 
-constexpr int kMaxVertIdx = 9;       // MAX_NUM_VERT_IDX   sort_vert_kernel.cu:6
-constexpr int kIntersectionOffset = 8; // INTERSECTION_OFFSET :7
-constexpr double kEps = 1e-8;        // EPSILON            :8 (a double literal in the reference)
-
-// "vertex 1 comes before vertex 2", vertices normalised around (0, 0): smallest on the positive x axis, growing anticlockwise
-// (sort_vert_kernel.cu:15-40; the reference falls off the end -- undefined -- when a y is exactly 0: false here).
-// Kept out of line: inlined twice into the selection loop, hipcc 7.2 at -O1 and above folds the second call to "false"
-// (every pick after the first stayed 0 on gfx950; -O0 and the out-of-line call agree with the CPU restatement).
-__device__ __noinline__ bool before(float x1, float y1, float x2, float y2)
-{
-    if ((double)fabsf(x1 - x2) < kEps && (double)fabsf(y2 - y1) < kEps) return false;
-    if (y1 > 0 && y2 < 0) return true;
-    if (y1 < 0 && y2 > 0) return false;
-    const float n1 = (float)((double)(x1 * x1 + y1 * y1) + kEps);
-    const float n2 = (float)((double)(x2 * x2 + y2 * y2) + kEps);
-    const float d = fabsf(x1) * x1 / n1 - fabsf(x2) * x2 / n2;
-    if (y1 > 0 && y2 > 0) return (double)d > kEps;
-    if (y1 < 0 && y2 < 0) return (double)d < kEps;
-    return false;
-}
+using vfa_eval::kIntersectionOffset;
+using vfa_eval::kMaxVertIdx;
 
 __global__ __launch_bounds__(256) void sort_vertices_kernel(const float *__restrict__ vertices, const uint8_t *__restrict__ mask,
                                                             const int *__restrict__ num_valid, int *__restrict__ idx, long long total,
@@ -49,42 +32,9 @@ __global__ __launch_bounds__(256) void sort_vertices_kernel(const float *__restr
     int pad = m - 1; // an arbitrary INVALID intersection point (the reference leaves it uninitialised when there is none)
     for (int j = kIntersectionOffset; j < m; ++j)
         if (!mk[j]) { pad = j; break; }
-    if (nv < 3) { // not enough vertices
-#pragma unroll
-        for (int j = 0; j < kMaxVertIdx; ++j) out[j] = pad;
-        return;
-    }
-    int order[kMaxVertIdx];
-#pragma unroll
-    for (int j = 0; j < kMaxVertIdx; ++j) order[j] = pad;
-    // selection sort: the j-th vertex is the smallest one that is larger than the (j - 1)-th          (:68-93)
-    float px = 0.0f, py = 0.0f; // previous pick
-    for (int j = 0; j < nv && j < kMaxVertIdx - 1; ++j) {
-        float x_min = 1.0f, y_min = (float)-kEps;
-        int take = 0;
-        for (int k = 0; k < m; ++k) {
-            const float x = v[2 * k], y = v[2 * k + 1];
-            if (mk[k] && before(x, y, x_min, y_min) && (j == 0 || before(px, py, x, y))) {
-                x_min = x; y_min = y; take = k;
-            }
-        }
-        order[j] = take;
-        px = v[2 * take];
-        py = v[2 * take + 1];
-    }
-    const int nvc = nv < kMaxVertIdx - 1 ? nv : kMaxVertIdx - 1;
-    order[nvc] = order[0]; // duplicate the first index                                                (:96)
-    // two identical boxes: the four corners of box 1 equal those of box 2                              (:107-121)
-    if (nv == 8) {
-        int counter = 0;
-        for (int j = 0; j < 4; ++j)
-            for (int k = 4; k < kIntersectionOffset; ++k)
-                if (order[k] == order[j]) ++counter;
-        if (counter == 4) {
-            order[4] = order[0];
-            for (int j = 5; j < kMaxVertIdx; ++j) order[j] = pad;
-        }
-    }
+    int order[kMaxVertIdx]; // the comparison and the selection loop: vfa_eval_sort.h, shared with the fused IoU kernel (vfa_iou.hip)
+    vfa_eval::order_polygon([&](int k, float &x, float &y) { x = v[2 * k]; y = v[2 * k + 1]; }, [&](int k) { return mk[k] != 0; }, nv, m,
+                            pad, order);
 #pragma unroll
     for (int j = 0; j < kMaxVertIdx; ++j) out[j] = order[j];
 }

@@ -6,6 +6,11 @@
 * ``BEVDecoder``  -- ``ObjectEncoder.nms / decode3d / decode2d`` (``vfa/data/encoder.py:230-305``) with the dataset constants
   passed explicitly: sigmoid + 5x5 max-pool NMS in one HIP kernel (``vfa_bev_nms_f32``), then top-k and the gathers (torch ops on
   the device: a few hundred numbers).
+* ``iou3d`` / ``iou_bev`` / ``iou3d_matrix`` / ``match_frames``  -- the reference's rotated-box ``IoU3D`` (``vfa/evaluation/pyeval/
+  IoU.py:206-225``) with one GPU lane per box pair (``vfa_iou3d_f32``, ``vfa_iou3d_frames_f32``): any batch shape, a whole
+  evaluation set per launch, the best ground truth of every detection without a host round trip per pair.
+* ``ap_aos_from_matches`` / ``ap_aos`` / ``evaluate_ap_aos``  -- the AP / AOS metric built on them (``evaluateAPAOS.py``);
+  ``evaluate_ap_aos`` has the signature and the 9-tuple of the reference's ``evaluateDetectionAPAOS``.
 """
 import numpy as np
 import torch
@@ -50,6 +55,206 @@ def bev_nms_batch(heatmap):
     conf = torch.empty_like(h)
     _lib.call("vfa_bev_nms_batch_f32", _lib.ptr(h), _lib.ptr(conf), B, L, W, _lib.current_stream_handle())
     return conf
+
+
+def _pair_ious(box1, box2, want_bev):
+    _lib.require_device(box1, box2)
+    if box1.shape != box2.shape or box1.dim() < 1 or box1.shape[-1] != 7:
+        raise ValueError(f"two box tensors of one shape (..., 7) are needed, got {tuple(box1.shape)} and {tuple(box2.shape)}")
+    lead = box1.shape[:-1]
+    a, b = (t.to(torch.float32).reshape(-1, 7).contiguous() for t in (box1, box2))
+    vol = torch.empty(a.shape[0], dtype=torch.float32, device=a.device)
+    bev = torch.empty_like(vol) if want_bev else None
+    _lib.call("vfa_iou3d_f32", _lib.ptr(a), _lib.ptr(b), _lib.ptr(vol), _lib.ptr(bev), a.shape[0], _lib.current_stream_handle())
+    return vol.reshape(lead), (bev.reshape(lead) if want_bev else None)
+
+
+def iou3d(box3d1, box3d2):
+    """The reference's ``IoU3D`` (IoU.py:206-225): boxes ``x y z l w h alpha``, ``(B, N, 7)`` like the reference's or any equal
+    leading shape (the reference itself only works on a single pair, IoU.py:27-28) -> IoUs of that leading shape.  Boxes apart in z
+    give a negative value like the reference's (its z overlap is not clamped)."""
+    return _pair_ious(box3d1, box3d2, False)[0]
+
+
+def iou_bev(box1, box2):
+    """Rotated-rectangle IoU, the first result of the reference's ``IoUs2D`` (IoU.py:178-204): boxes ``x y w h alpha``,
+    ``(..., 5)`` -> ``(...)``."""
+    _lib.require_device(box1, box2)
+    if box1.shape != box2.shape or box1.dim() < 1 or box1.shape[-1] != 5:
+        raise ValueError(f"two box tensors of one shape (..., 5) are needed, got {tuple(box1.shape)} and {tuple(box2.shape)}")
+
+    def lift(b):  # a unit-height box at z = 0 over the rectangle
+        b = b.to(torch.float32)
+        return torch.stack([b[..., 0], b[..., 1], torch.zeros_like(b[..., 0]), b[..., 2], b[..., 3], torch.ones_like(b[..., 0]),
+                            b[..., 4]], dim=-1)
+    return _pair_ious(lift(box1), lift(box2), True)[1]
+
+
+def _frames_call(det, det_begin, gt, gt_begin, n_frames, pair_begin, n_pairs, want_matrix, want_best):
+    dev = det.device
+    iou = torch.empty(n_pairs, dtype=torch.float32, device=dev) if want_matrix else None
+    best_idx = torch.full((det.shape[0],), -1, dtype=torch.int32, device=dev) if want_best else None
+    best_iou = torch.full((det.shape[0],), -1.0, dtype=torch.float32, device=dev) if want_best else None
+    _lib.call("vfa_iou3d_frames_f32", _lib.ptr(det), _lib.ptr(det_begin), _lib.ptr(gt), _lib.ptr(gt_begin), n_frames, det.shape[0],
+              gt.shape[0], _lib.ptr(pair_begin), n_pairs, _lib.ptr(iou), _lib.ptr(best_idx), _lib.ptr(best_iou),
+              _lib.current_stream_handle())
+    return iou, best_idx, best_iou
+
+
+def _box_rows(t, name):
+    if t.dim() != 2 or t.shape[1] != 7:
+        raise ValueError(f"{name} must be (n, 7) boxes x y z l w h alpha, got {tuple(t.shape)}")
+    return t.to(torch.float32).contiguous()
+
+
+def iou3d_matrix(det, gt):
+    """``det (P, 7)``, ``gt (G, 7)`` -> the ``(P, G)`` matrix of 3D IoUs, one lane per pair in one launch."""
+    _lib.require_device(det, gt)
+    det, gt = _box_rows(det, "det"), _box_rows(gt, "gt")
+    P, G = det.shape[0], gt.shape[0]
+    det_begin = torch.tensor([0, P], dtype=torch.int32, device=det.device)
+    gt_begin = torch.tensor([0, G], dtype=torch.int32, device=det.device)
+    pair_begin = torch.tensor([0, P * G], dtype=torch.int64, device=det.device)
+    iou, _, _ = _frames_call(det, det_begin, gt, gt_begin, 1, pair_begin, P * G, True, False)
+    return iou.reshape(P, G)
+
+
+def match_frames(det, det_frame, gt, gt_frame, n_frames=None, with_matrix=False):
+    """The best ground truth of every detection of an evaluation set, in one launch (``vfa_iou3d_frames_f32``).
+
+    ``det (P, 7)``, ``gt (G, 7)`` boxes; ``det_frame (P)``, ``gt_frame (G)`` integer frame counters ``0 .. n_frames - 1``, each
+    NON-DECREASING (rows sorted by frame).  ``n_frames``: given by the caller, nothing here waits for the device; ``None``: taken
+    from the largest counter, which costs one host synchronisation (and checks the order while it is at it).  With ``n_frames`` given
+    the counters are NOT checked: unsorted or out-of-range ones stay within the arrays but give meaningless matches.
+    Returns ``best_idx (P)`` int32 -- index of the ground truth WITHIN ITS FRAME with the largest IoU, the lowest index on a tie,
+    -1 when the frame has no ground truth (or only NaN IoUs) -- and ``best_iou (P)`` (-1 there).  A threshold ``t > 0`` of the
+    metric is then ``best_iou >= t`` (see include/vfa_hip.h for why that equals the reference's scan).
+    ``with_matrix=True`` also fills the frames' IoU matrices and returns ``(best_idx, best_iou, iou, pair_begin)``: frame ``f``'s
+    ``(P_f, G_f)`` matrix is ``iou[pair_begin[f]:pair_begin[f + 1]]``, detection-major (one more synchronisation, for its size)."""
+    _lib.require_device(det, det_frame, gt, gt_frame)
+    det, gt = _box_rows(det, "det"), _box_rows(gt, "gt")
+    det_frame, gt_frame = det_frame.to(torch.int64).contiguous(), gt_frame.to(torch.int64).contiguous()
+    if det_frame.shape != (det.shape[0],) or gt_frame.shape != (gt.shape[0],):
+        raise ValueError("one frame counter per box is needed")
+    dev = det.device
+    if n_frames is None:
+        both = torch.cat([det_frame, gt_frame])
+        if both.numel() == 0:
+            n_frames = 0
+        else:
+            ordered = torch.stack([(det_frame[1:] >= det_frame[:-1]).all(), (gt_frame[1:] >= gt_frame[:-1]).all(), both.min() >= 0])
+            hi, ok = int(both.max()), bool(ordered.all())
+            if not ok:
+                raise ValueError("match_frames: frame counters must be non-negative and sorted (non-decreasing)")
+            n_frames = hi + 1
+    edges = torch.arange(n_frames + 1, dtype=torch.int64, device=dev)
+    det_begin64, gt_begin64 = torch.searchsorted(det_frame, edges), torch.searchsorted(gt_frame, edges)
+    det_begin, gt_begin = det_begin64.to(torch.int32), gt_begin64.to(torch.int32)
+    if not with_matrix:
+        _, best_idx, best_iou = _frames_call(det, det_begin, gt, gt_begin, n_frames, None, 0, False, True)
+        return best_idx, best_iou
+    pair_begin = torch.zeros(n_frames + 1, dtype=torch.int64, device=dev)
+    pair_begin[1:] = torch.cumsum((det_begin64[1:] - det_begin64[:-1]) * (gt_begin64[1:] - gt_begin64[:-1]), 0)
+    iou, best_idx, best_iou = _frames_call(det, det_begin, gt, gt_begin, n_frames, pair_begin, int(pair_begin[-1]), True, True)
+    return best_idx, best_iou, iou, pair_begin
+
+
+def ap_aos_from_matches(conf, matched, delta_rot, n_gt):
+    """The tail of the reference's ``CLEAR_MOD_HUN2`` (evaluateAPAOS.py:21-65) from the match table.
+
+    ``conf (N)`` confidences, ``matched (N)`` true where the detection has a ground truth (TP), ``delta_rot (N)`` its angle
+    difference in radians (read only where matched), ``n_gt`` the number of ground truths (``all_P``).  Detections in descending
+    confidence; precision ``TP / (TP + FP)``, recall ``TP / n_gt`` and the running orientation similarity
+    ``cumsum(tp (1 + cos delta) / 2) / (i + 1)`` as prefix sums (the reference's is a quadratic loop); then the 11 recall points
+    ``arange(0, 1.1, 0.1)``: the maximum of the tail that starts at the first detection whose recall reaches the point, 0 when none
+    does.  float64 like the reference's numpy, plain torch ops on the device the inputs live on.  Returns ``(AP, AOS)`` as fractions.
+    Equal confidences: the order among them is unspecified, here as in the reference (whose reversed argsort is not stable)."""
+    if n_gt <= 0:
+        raise ValueError("ap_aos_from_matches: n_gt must be positive (recall is TP / n_gt)")
+    conf = torch.as_tensor(conf).to(torch.float64)
+    dev = conf.device
+    n = conf.numel()
+    if n == 0:
+        return 0.0, 0.0
+    order = torch.argsort(conf, descending=True)
+    tp = torch.as_tensor(matched, device=dev).to(torch.bool)[order]
+    delta = torch.as_tensor(delta_rot, device=dev).to(torch.float64)[order]
+    rank = torch.arange(1, n + 1, dtype=torch.float64, device=dev)
+    ctp = torch.cumsum(tp.to(torch.float64), 0)
+    precision, recall = ctp / rank, ctp / float(n_gt)
+    sim = torch.where(tp, (1 + torch.cos(delta)) / 2, torch.zeros_like(delta))
+    aos = torch.cumsum(sim, 0) / rank
+    points = torch.as_tensor(np.arange(0, 1.1, 0.1), dtype=torch.float64, device=dev)
+    first = torch.searchsorted(recall.contiguous(), points)          # recall never decreases: the first index that reaches the point
+    reached, first = first < n, first.clamp(max=n - 1)
+
+    def eleven_point(curve):
+        tail_max = torch.flip(torch.cummax(torch.flip(curve, [0]), 0).values, [0])
+        return float(torch.where(reached, tail_max[first], torch.zeros_like(points)).sum() / 11)
+    return eleven_point(precision), eleven_point(aos)
+
+
+def _table(a, width, name):
+    a = np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+    a = a.reshape(-1, width) if a.size == 0 else np.atleast_2d(a)
+    if a.shape[1] != width:
+        raise ValueError(f"{name}: {width} columns are needed, got {a.shape[1]}")
+    return a
+
+
+def ap_aos(gt, det, thresholds=(0.75, 0.5, 0.25), device="cuda"):
+    """AP and AOS of a detection set at each IoU threshold -> ``[(AP, AOS), ...]`` as fractions, one launch for all the IoUs.
+
+    Arrays in the reference's text-file layout (evaluateAPAOS.py:121-122): ``gt`` rows ``frame x y z l w h rotation``, ``det`` rows
+    ``frame x y z l w h rotation conf``.  The bookkeeping is the reference's: the frames are those that HAVE detections
+    (:111, :123), ground truth of other frames does not count; several detections may match one ground truth; a detection is a
+    true positive when its best IoU reaches the threshold.  Kept quirk: ``CLEAR_MOD_HUN2`` walks the frame counters up to the
+    last frame that has ground truth (:10-12), so detections of later frames are dropped while frames in between that have
+    detections and no ground truth count as false positives.  One deviation: the reference calls a detection a true positive when
+    its row holds no -1 (:98), which also rejects a matched detection whose confidence or angle difference is exactly -1.0; here
+    "has a match" decides."""
+    thresholds = [float(t) for t in thresholds]
+    if not thresholds or min(thresholds) <= 0 or any(t != t for t in thresholds):
+        raise ValueError("ap_aos: IoU thresholds must be > 0 (one best match per detection serves every positive threshold only)")
+    gt, det = _table(gt, 8, "gt"), _table(det, 9, "det")
+    if det.shape[0] == 0:
+        raise ValueError("detection is empty")
+    frames = np.unique(det[:, 0])
+    det_ctr = np.searchsorted(frames, det[:, 0])
+    det = det[np.argsort(det_ctr, kind="stable")]
+    det_ctr = np.sort(det_ctr)
+    gt = gt[np.isin(gt[:, 0], frames)]
+    if gt.shape[0] == 0:
+        raise ValueError("no ground truth in the frames that have detections")
+    gt_ctr = np.searchsorted(frames, gt[:, 0])
+    gt = gt[np.argsort(gt_ctr, kind="stable")]
+    gt_ctr = np.sort(gt_ctr)
+    n_frames = int(gt_ctr.max()) + 1
+    det, det_ctr = det[det_ctr < n_frames], det_ctr[det_ctr < n_frames]
+    dev = torch.device(device)
+    best_idx, best_iou = match_frames(torch.from_numpy(det[:, 1:8]).to(dev), torch.from_numpy(det_ctr).to(dev),
+                                      torch.from_numpy(gt[:, 1:8]).to(dev), torch.from_numpy(gt_ctr).to(dev), n_frames=n_frames)
+    best_idx, best_iou = best_idx.cpu().numpy(), best_iou.cpu().numpy()
+    gt_first = np.searchsorted(gt_ctr, det_ctr)                       # row of the frame's first ground truth
+    gt_rot = gt[np.clip(gt_first + best_idx, 0, gt.shape[0] - 1), 7]
+    out = []
+    for t in thresholds:
+        matched = (best_idx >= 0) & (best_iou >= np.float32(t))
+        delta = np.where(matched, det[:, 7] - gt_rot, 0.0)
+        out.append(ap_aos_from_matches(torch.from_numpy(det[:, 8].copy()), torch.from_numpy(matched), torch.from_numpy(delta),
+                                       gt.shape[0]))
+    return out
+
+
+def evaluate_ap_aos(res_fpath, gt_fpath):
+    """The reference's ``evaluateDetectionAPAOS(res_fpath, gt_fpath)`` (evaluateAPAOS.py:107-170): two text files ->
+    ``(AP_75, AOS_75, OS_75, AP_50, AOS_50, OS_50, AP_25, AOS_25, OS_25)``, AP and AOS in per cent, OS = AOS / AP (NaN when AP is 0)."""
+    gt_raw, det_raw = np.loadtxt(gt_fpath, ndmin=2), np.loadtxt(res_fpath, ndmin=2)
+    assert det_raw.shape[0] != 0, "detection is empty"
+    out = []
+    for ap, aos in ap_aos(gt_raw, det_raw, (0.75, 0.5, 0.25)):
+        out += [ap * 100, aos * 100, aos / ap if ap else float("nan")]
+    return tuple(out)
 
 
 class BEVDecoder:
