@@ -281,3 +281,68 @@ def test_sliver_shift_bound_and_fp16_headroom_on_the_hard_cells(oracle):
                     largest = max(largest, float((peak[vis] * 2.0 ** (ea - sh[vis])).max()))
     print(f"[slivers] largest scaled voxel feature on the hard cells {largest:.1f} = 65504 / {65504 / largest:.0f}; {shifted} boxes with a shift")
     assert shifted > 0 and largest * 8.0 <= 65504.0
+
+
+def _sliver_frame(oracle, nl):
+    """The diagonal rig with the upper clamp one step above the left edge of one box (test_largest_reachable_shift_next_to_honest_boxes):
+    one tile of the 16 x 32 sub-grid holds a sliver, the others hold honest boxes only.  -> the geometry operands on the device."""
+    from vfa_amd import _lib
+    wl = _diagonal_rig(nl)
+    dev = torch.device("cuda:0")
+    L, W = wl["grid"].shape[1:3]
+    zl = oracle.z_layers_of(wl["grid_height"], wl["cube_size"])
+    co = oracle.corner_offsets(wl["cube_size"])
+    grid_np = wl["grid"][0].reshape(-1, 3).numpy()
+    Hf, Wf = wl["features"][0][0].shape[-2:]
+    box, _, _ = oracle.box_params(wl["calibs"][0].numpy(), grid_np, zl, co, "MultiviewC", (2160, 2160), Hf, Wf)
+    target = (L // 2 + 1) * W + W // 2 + 3
+    crange = (-1.0, float(np.nextafter(box[0, target, 0], np.float32(2.0))))
+    geo = (wl["calibs"].to(dev), wl["grid"].to(dev), torch.from_numpy(np.asarray(zl, np.float32)).to(dev),
+           torch.from_numpy(np.asarray(co, np.float32)).to(dev), _lib.CONV_KIND["MultiviewC"], (2160, 2160))
+    return geo, crange, (L, W), (Hf, Wf)
+
+
+@pytest.mark.parametrize("nl", [1, 4])
+def test_backward_shifts_are_the_shifts_of_the_record_kernels(oracle, nl):
+    """The training backward rescales the rows of its recomputed fp16 product by ``ops.sliver_shifts``; the forward scaled them by
+    what the record kernels left in the workspace.  Both must be the per-box shift (the box parameter kernel's area and visibility,
+    this file's restatement of ``sliver_shift``) reduced over the forward's unit: nl = 1, the serial kernel -- (view, tile, scale), bits
+    8-15 of the tile header flags of ``ops.frame_records``; nl > 1, the pipelined kernel -- (tile, scale) over all views and layers, the
+    ``shifts`` region of ``ops.pipe_records``.  On a frame with a sliver by construction: shifted and unshifted tiles both occur."""
+    from vfa_amd import ops
+    (calibs, grid, zl, co, kind, image_wh), crange, (L, W), (Hf, Wf) = _sliver_frame(oracle, nl)
+    n = calibs.shape[0]
+    tiles_l, tiles_w = (L + TILE_L - 1) // TILE_L, (W + TILE_W - 1) // TILE_W
+    _, area, vis = ops.box_params(calibs, grid.reshape(-1, 3), zl, co, kind, image_wh, (Hf, Wf), crange)
+    area, vis = area.cpu().numpy(), vis.cpu().numpy().astype(bool)                      # (n, nl, cells)
+    per_box = np.where(vis, _sliver_shift(area, Hf, Wf), 0)
+    cell = np.arange(L * W)
+    tile_of = (cell // W) // TILE_L * tiles_w + (cell % W) // TILE_W                    # (cells)
+    per_item = np.zeros((n, tiles_l * tiles_w), np.int64)                               # (view, tile): max over layers and boxes
+    for v in range(n):
+        np.maximum.at(per_item[v], np.broadcast_to(tile_of, per_box[v].shape).reshape(-1), per_box[v].reshape(-1))
+    per_tile = per_item.max(axis=0)                                                     # (tile): ... and views
+    assert (per_tile > 0).any() and (per_tile == 0).any(), per_tile
+    if nl > 1:
+        got = ops.sliver_shifts(calibs, grid, zl, co, kind, image_wh, (Hf, Wf), per_item=False, crange=crange)
+        torch.cuda.synchronize()
+        assert tuple(got.shape) == (1, L * W)
+        np.testing.assert_array_equal(got[0].cpu().numpy().astype(np.int64), per_tile[tile_of])
+        ws = ops.pipe_records(calibs, grid, zl, co, kind, image_wh, [(Hf, Wf)], crange=crange, cuts=False)
+        torch.cuda.synchronize()
+        at = ops.pipe_workspace_layout(n, L, W, nl, 1)["shifts"][0]
+        in_ws = ws[at:at + 4 * tiles_l * tiles_w].cpu().numpy().view(np.uint32).astype(np.int64)
+        np.testing.assert_array_equal(in_ws, per_tile)
+        np.testing.assert_array_equal(in_ws[tile_of], got[0].cpu().numpy().astype(np.int64))
+    else:
+        got = ops.sliver_shifts(calibs, grid, zl, co, kind, image_wh, (Hf, Wf), per_item=True, crange=crange)
+        torch.cuda.synchronize()
+        assert tuple(got.shape) == (n, L * W)
+        np.testing.assert_array_equal(got.cpu().numpy().astype(np.int64), per_item[:, tile_of])
+        ws = ops.frame_records(calibs, grid, zl, co, kind, image_wh, [(Hf, Wf)], crange=crange, cuts=False)
+        torch.cuda.synchronize()
+        at = ops.frame_workspace_layout(n, L, W, 1)["hdrs"][0]
+        hdr = ws[at:at + 32 * n * tiles_l * tiles_w].cpu().numpy().view(np.uint32).reshape(n, tiles_l * tiles_w, 8)
+        in_ws = ((hdr[:, :, 0] >> 8) & 0xff).astype(np.int64)                           # bits 8-15 of the header flags
+        np.testing.assert_array_equal(in_ws, per_item)
+        np.testing.assert_array_equal(in_ws[:, tile_of], got.cpu().numpy().astype(np.int64))

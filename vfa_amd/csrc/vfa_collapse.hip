@@ -22,10 +22,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "vfa_hip.h"
+#include "vfa_geom.h"
 
 
 namespace {
+using vfa_dev::relu_t;
 
 constexpr int kRows = 32;         // cells per tile = one 32x32 MFMA row block
 constexpr int kK = 256, kN = 256; // the only shape this kernel is built for
@@ -41,8 +42,6 @@ constexpr int kDmaPerItem = kRows / (kThreads / 64);      // LDS-DMA instruction
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float relu_t(float x) { return (x < 0.0f) ? 0.0f : x; } // NaN stays NaN
 
 // x = hi + lo + r exactly in fp32 arithmetic: hi = RNE bf16(x), lo = RNE bf16(x - hi)
 __device__ __forceinline__ void split_bf16(float x, __bf16 &hi, __bf16 &lo)

@@ -87,18 +87,8 @@ __global__ __launch_bounds__(256) void det_emit_kernel(BoxGeom g, int nl, int ce
     const int layer = (int)(b % nl);
     const long long vc = b / nl;
     const int cell = cell_begin + (int)(vc % cell_count), view = (int)(vc / cell_count);
-    const float *P = g.calibs + (size_t)view * 12;
-    const float gx = g.grid[cell * 3 + 0] + 0.0f; // + the int64 zeros of z_corners (vfa_op.py:52, :64), as the forward
-    const float gy = g.grid[cell * 3 + 1] + 0.0f;
-    const float gz = g.grid[cell * 3 + 2] + g.z_layers[layer];
-    float l = 0.0f, t = 0.0f, r = 0.0f, bt = 0.0f;
-#pragma unroll 1
-    for (int k = 0; k < 8; ++k) {
-        float nu, nv;
-        project_corner(g, P, gx, gy, gz, k, nu, nv);
-        if (k == 0) { l = r = nu; t = bt = nv; }
-        else { l = min_t(l, nu); r = max_t(r, nu); t = min_t(t, nv); bt = max_t(bt, nv); }
-    }
+    float l, t, r, bt;
+    cube_box(g, g.calibs + (size_t)view * 12, cell, layer, l, t, r, bt); // the forward's box
     const float area = box_area(l, t, r, bt, Hf, Wf);
     const unsigned long long rec0 = (unsigned long long)(16 * b);
     unsigned long long *kb = keys + 16 * b;

@@ -27,6 +27,7 @@
 
 #include "vfa_geom.h"
 #include "vfa_split.h"
+#include "vfa_tile.h"
 
 #ifndef VFA_TICKET_ORDER
 // The hand-off ticket of a tile cut between workgroups (flush): a RELAXED agent-scope add by one lane behind a workgroup barrier.
@@ -40,12 +41,8 @@
 namespace {
 using namespace vfa_dev;
 
-constexpr int kTileW = 8, kTileL = 4, kTileBoxes = kTileW * kTileL; // 32 cells = one 32-row MFMA block
-constexpr int kC = 256;                                             // channels in = channels out
-constexpr int kRecBytes = 96, kHdrBytes = 32;
-constexpr int kMaxScales = 3;
-constexpr int kSlotBytes = kC * 4;                                  // one tap = 256 fp32
-constexpr int kMaxSlots = 123;                                      // LDS tap window of a (tile, view, scale)
+constexpr int kRecBytes = 96;                                       // (vfa_pipe.hip: 48 -- the tap weights are spelled out here)
+constexpr int kMaxSlots = 123;                                      // LDS tap window of a (tile, view, scale) (vfa_pipe.hip: kWinSlots quarter slots)
 // cost estimate of an item of the persistent kernel in units of 16 cycles (tile_chunks_kernel): base + 1 per window slot
 constexpr unsigned kItemCost = 704, kRowItemCost = 522; // (unit: 16 cycles -- refitted in the second session of round 5, see tile_chunks_kernel)
 constexpr int kRecSlots = 3;                                        // + the 32 box records of the item (3 KiB) behind it
@@ -55,16 +52,12 @@ constexpr int kPlane = kTileBoxes * kRowBytes;                      // 16 KiB
 constexpr int kSteps = kC / 16;                                     // k-steps of v_mfma_f32_32x32x16_bf16
 
 // record flags
-constexpr int kVis = 1, kCont = 1 << 8; // bits 1-2 DXC, bits 3-4 DYC; kCont: same tap set as the previous box of the 4-box chunk
+constexpr int kCont = 1 << 8; // (bit 0 kVis,) bits 1-2 DXC, bits 3-4 DYC; kCont: same tap set as the previous box of the 4-box chunk
 // tile header flags
-constexpr int kTileLive = 1, kTileDirect = 2, kTileRows = 4; // kTileRows: a direct item whose pooled rows the pre-pass leaves in the workspace (header word 2 = its slot there)
+constexpr int kTileRows = 4; // (behind kTileLive, kTileDirect) kTileRows: a direct item whose pooled rows the pre-pass leaves in the workspace (header word 2 = its slot there)
 constexpr int kTileShiftAt = 8; // bits 8-15: the item's sliver shift (vfa_geom.h): binary places its voxel features are scaled down by in the fp16 split
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-struct ScaleDims { int Hf, Wf; };
 
 struct RecordArgs {
     BoxGeom g;
@@ -82,8 +75,6 @@ struct RecordArgs {
     int views_pad;                   // n_views rounded up to 8
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 // ------------------------------------------------------------------------------------------------
 // 1. geometry of the frame: one half-wave (32 lanes) per (view, tile), lane = cell of the tile (4 rows of 8)
 // ------------------------------------------------------------------------------------------------
@@ -92,31 +83,13 @@ __global__ __launch_bounds__(kWave) void frame_records_kernel(RecordArgs a)
     // the 32 records of a (view, tile) are 3 KiB of consecutive memory: staged here so that the half-wave writes them as six
     // 512-byte rows instead of 32 x 6 scattered 16-byte pieces (the kernel was bound by those stores)
     __shared__ uint4 stage[2][kTileBoxes * 6];
-    const int lane = threadIdx.x, half = lane >> 5, b = lane & 31;
-    const long long pair = (long long)blockIdx.x * 2 + half;
-    const bool pair_ok = pair < (long long)a.n_views * a.n_tiles;
-    const int view = pair_ok ? (int)(pair / a.n_tiles) : 0, tile = pair_ok ? (int)(pair % a.n_tiles) : 0;
-    const int tl = tile / a.tiles_w, tw = tile - tl * a.tiles_w;
-    const int cl = tl * kTileL + (b >> 3), cw = tw * kTileW + (b & 7);
-    const bool valid = pair_ok && cl < a.L && cw < a.W;
-    const int cell = valid ? cl * a.W + cw : 0;
+    const TileLane ln = tile_lane(a.n_views, a.n_tiles, a.tiles_w, a.L, a.W);
+    const int lane = threadIdx.x, half = ln.half, b = ln.b, view = ln.view, tile = ln.tile;
+    const bool pair_ok = ln.pair_ok, valid = ln.valid;
 
     // the cube once per (view, cell): scale-independent                     vfa_op.py:64-88, utils.py:56-59
     float l, t, r, bt;
-    {
-        const float *P = a.g.calibs + (size_t)view * 12;
-        const float gx = a.g.grid[cell * 3 + 0] + 0.0f; // + the int64 zeros of z_corners (vfa_op.py:52, :64)
-        const float gy = a.g.grid[cell * 3 + 1] + 0.0f;
-        const float gz = a.g.grid[cell * 3 + 2] + a.g.z_layers[0];
-        l = t = r = bt = 0.0f;
-#pragma unroll 1
-        for (int k = 0; k < 8; ++k) {
-            float nu, nv;
-            project_corner(a.g, P, gx, gy, gz, k, nu, nv);
-            if (k == 0) { l = r = nu; t = bt = nv; }
-            else { l = min_t(l, nu); r = max_t(r, nu); t = min_t(t, nv); bt = max_t(bt, nv); }
-        }
-    }
+    cube_box(a.g, a.g.calibs + (size_t)view * 12, ln.cell, 0, l, t, r, bt);
 #pragma unroll 1
     for (int s = 0; s < a.n_scales; ++s) {
         const int Hf = a.dims[s].Hf, Wf = a.dims[s].Wf;
@@ -124,52 +97,19 @@ __global__ __launch_bounds__(kWave) void frame_records_kernel(RecordArgs a)
         const bool vis = valid && box_visible(area, Hf, Wf);                                  // :106
         const float masked = valid ? area * 0.0f : 0.0f; // value of a masked voxel: 0, or NaN when the box itself is NaN
         const bool live_box = vis || (valid && masked != masked);
-        const Axis xl = make_axis(l, Wf), xr = make_axis(r, Wf), yt = make_axis(t, Hf), yb = make_axis(bt, Hf);
-        const int dx = xr.i0 - xl.i0, dy = yb.i0 - yt.i0;
+        const BoxTaps tp = box_taps(l, t, r, bt, Hf, Wf);
+        const int dx = tp.xr.i0 - tp.xl.i0, dy = tp.yb.i0 - tp.yt.i0;
         const int dxc = dx == 0 ? 0 : (dx == 1 ? 1 : 2), dyc = dy == 0 ? 0 : (dy == 1 ? 1 : 2);
-        // tap coordinates, out-of-image taps redirected to the zero border (coordinate -1 or Hf / Wf)
-        const int xs[4] = {clampi(xl.i0, -1, Wf), clampi(xl.i0 + 1, -1, Wf), clampi(xr.i0, -1, Wf), clampi(xr.i0 + 1, -1, Wf)};
-        const int ys[4] = {clampi(yt.i0, -1, Hf), clampi(yt.i0 + 1, -1, Hf), clampi(yb.i0, -1, Hf), clampi(yb.i0 + 1, -1, Hf)};
-        // window of the tile over its VISIBLE boxes: columns [x0, x1], top rows [t0, t1], bottom rows [b0, b1]
-        constexpr int kBig = 1 << 20;
-        int x0 = vis ? min(xs[0], xs[2]) : kBig, x1 = vis ? max(xs[1], xs[3]) : -kBig;
-        int t0 = vis ? ys[0] : kBig, t1 = vis ? ys[1] : -kBig, b0 = vis ? ys[2] : kBig, b1 = vis ? ys[3] : -kBig;
-        // binary places the fp16 split of the item gives up for its noisiest visible box (vfa_geom.h: sliver_shift; 0 for honest boxes)
-        int shift = vis ? sliver_shift(area, Hf, Wf) : 0;
-#pragma unroll
-        for (int m = 1; m < 32; m <<= 1) {
-            x0 = min(x0, __shfl_xor(x0, m, 32)); x1 = max(x1, __shfl_xor(x1, m, 32));
-            t0 = min(t0, __shfl_xor(t0, m, 32)); t1 = max(t1, __shfl_xor(t1, m, 32));
-            b0 = min(b0, __shfl_xor(b0, m, 32)); b1 = max(b1, __shfl_xor(b1, m, 32));
-            shift = max(shift, __shfl_xor(shift, m, 32));
-        }
-        const unsigned long long vis_all = __ballot(vis), live_all = __ballot(live_box);
-        const bool any_vis = ((vis_all >> (32 * half)) & 0xffffffffull) != 0ull;
-        const bool any_live = ((live_all >> (32 * half)) & 0xffffffffull) != 0ull;
-        int cwid = 0, top_rows = 0, bot_rows = 0, n_slots = 0;
-        if (any_vis) {
-            cwid = x1 - x0 + 1;
-            if (b0 <= t1 + 1) { // the bands touch or overlap: one band [t0, max(t1, b1)]
-                top_rows = max(t1, b1) - t0 + 1;
-                bot_rows = 0;
-                b0 = t0 + top_rows; // rows >= b0 would start the (empty) second band
-            } else {
-                top_rows = t1 - t0 + 1;
-                bot_rows = b1 - b0 + 1;
-            }
-            n_slots = cwid * (top_rows + bot_rows);
-        }
-        const bool direct = n_slots > kMaxSlots;
-        auto slot_row = [&](int y) { return y < t0 + top_rows ? y - t0 : top_rows + (y - b0); };
+        const TileWindow tw = tile_window(tp, vis, live_box, area, Hf, Wf, half);
+        const Window &win = tw.w;
+        const bool any_live = tw.any_live;
+        const int shift = tw.shift, n_slots = win.n_slots;
+        const bool direct = n_slots > kMaxSlots; // (vfa_pipe.hip: its own capacity, a launch argument)
         unsigned rows[4], cols[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (direct) { rows[k] = (unsigned)(ys[k] + 1); cols[k] = (unsigned)(xs[k] + 1); }
-            else { rows[k] = (unsigned)(slot_row(ys[k]) * cwid); cols[k] = (unsigned)(xs[k] - x0); }
-        }
+        tap_parts(win, tp, direct, rows, cols);
         // boxes that continue the tap set of their left neighbour inside a 4-box chunk reuse its register patch
         const int tag = (vis ? 1 : 0) | (dxc << 1) | (dyc << 3);
-        const unsigned kx = (unsigned)(xs[0] + 1) | ((unsigned)(xs[2] + 1) << 16), ky = (unsigned)(ys[0] + 1) | ((unsigned)(ys[2] + 1) << 16);
+        const unsigned kx = (unsigned)(tp.xs[0] + 1) | ((unsigned)(tp.xs[2] + 1) << 16), ky = (unsigned)(tp.ys[0] + 1) | ((unsigned)(tp.ys[2] + 1) << 16);
         const int tag_p = __shfl_up(tag, 1);
         const unsigned kx_p = __shfl_up(kx, 1), ky_p = __shfl_up(ky, 1);
         const bool cont = vis && (b & 3) != 0 && tag_p == tag && kx_p == kx && ky_p == ky;
@@ -177,10 +117,10 @@ __global__ __launch_bounds__(kWave) void frame_records_kernel(RecordArgs a)
         float w[16];
         {
             float q[4];
-            bilinear_weights(q, xl, yt); w[0] = q[0]; w[1] = q[1]; w[2] = q[2]; w[3] = q[3];       // lt
-            bilinear_weights(q, xr, yb); w[4] = q[0]; w[5] = q[1]; w[6] = q[2]; w[7] = q[3];       // rb
-            bilinear_weights(q, xr, yt); w[8] = q[0]; w[9] = q[1]; w[10] = q[2]; w[11] = q[3];     // rt
-            bilinear_weights(q, xl, yb); w[12] = q[0]; w[13] = q[1]; w[14] = q[2]; w[15] = q[3];   // lb
+            bilinear_weights(q, tp.xl, tp.yt); w[0] = q[0]; w[1] = q[1]; w[2] = q[2]; w[3] = q[3];       // lt
+            bilinear_weights(q, tp.xr, tp.yb); w[4] = q[0]; w[5] = q[1]; w[6] = q[2]; w[7] = q[3];       // rb
+            bilinear_weights(q, tp.xr, tp.yt); w[8] = q[0]; w[9] = q[1]; w[10] = q[2]; w[11] = q[3];     // rt
+            bilinear_weights(q, tp.xl, tp.yb); w[12] = q[0]; w[13] = q[1]; w[14] = q[2]; w[15] = q[3];   // lb
         }
         if (pair_ok) {
             uint4 *st = stage[half] + b * 6;
@@ -200,8 +140,7 @@ __global__ __launch_bounds__(kWave) void frame_records_kernel(RecordArgs a)
             for (int k = 0; k < 6; ++k) rec[k * 32 + b] = stage[half][k * 32 + b];
             if (b == 0) {
                 uint4 *hdr = reinterpret_cast<uint4 *>(a.hdrs[s] + ((size_t)view * a.n_tiles + tile) * kHdrBytes);
-                const int inv = cwid > 0 ? (65536 + cwid - 1) / cwid : 0; // floor(s / cwid) == (s * inv) >> 16 for s < 128
-                unsigned hflags = (any_live ? kTileLive : 0) | (direct ? kTileDirect : 0) | ((unsigned)shift << kTileShiftAt), word2 = (unsigned)cwid;
+                unsigned hflags = (any_live ? kTileLive : 0) | (direct ? kTileDirect : 0) | ((unsigned)shift << kTileShiftAt), word2 = (unsigned)win.cwid;
                 if (any_live) atomicOr(a.live[s] + tile, 1u << view);
                 if (any_live && direct) {
                     atomicOr(a.direct[s] + tile, 1u << view);
@@ -215,8 +154,8 @@ __global__ __launch_bounds__(kWave) void frame_records_kernel(RecordArgs a)
                 const bool main_item = any_live && !(direct && !(hflags & kTileRows));
                 a.item_w[((size_t)tile * kMaxScales + s) * a.views_pad + view] =
                     (unsigned short)(!main_item ? 0u : (direct ? kRowItemCost : kItemCost + (unsigned)n_slots));
-                hdr[0] = make_uint4(hflags, (unsigned)n_slots, word2, (unsigned)inv);
-                hdr[1] = make_uint4((unsigned)x0, (unsigned)t0, (unsigned)top_rows, (unsigned)b0);
+                hdr[0] = tile_header0(hflags, win, word2);
+                hdr[1] = tile_header1(win);
             }
         }
         __syncthreads(); // the stage is reused by the next scale
@@ -226,9 +165,9 @@ __global__ __launch_bounds__(kWave) void frame_records_kernel(RecordArgs a)
 }
 
 // The sliver shifts of a frame as the BACKWARD of training needs them (vfa_collapse_gemm_relu_backward_f16_f32): per row of the
-// recomputed product the binary places its item was scaled down by in the forward.  Same projection, same area, same sliver_shift as
-// frame_records_kernel / pipe_records_kernel.  per_item: the serial kernel's unit (view, tile, scale) -> out[view][cell]; else the
-// pipelined kernel's (tile, scale) over all views and layers -> tile_max[tile] (atomicMax), expanded by sliver_expand_kernel.
+// recomputed product the binary places its item was scaled down by in the forward: the box of `cube_box`, its `box_area`,
+// `box_visible` and `sliver_shift` (vfa_geom.h), the definitions the two record kernels build on.  per_item: the serial kernel's unit
+// (view, tile, scale) -> out[view][cell]; else the pipelined kernel's (tile, scale) over all views and layers -> tile_max[tile] (atomicMax), expanded by sliver_expand_kernel.
 struct ShiftArgs {
     BoxGeom g;
     int n_views, L, W, tiles_w, n_tiles, nl, Hf, Wf, per_item;
@@ -237,35 +176,21 @@ struct ShiftArgs {
 };
 __global__ __launch_bounds__(kWave) void sliver_shift_kernel(ShiftArgs a)
 {
-    const int lane = threadIdx.x, half = lane >> 5, b = lane & 31;
-    const long long pair = (long long)blockIdx.x * 2 + half;
-    const bool pair_ok = pair < (long long)a.n_views * a.n_tiles;
-    const int view = pair_ok ? (int)(pair / a.n_tiles) : 0, tile = pair_ok ? (int)(pair % a.n_tiles) : 0;
-    const int tl = tile / a.tiles_w, tw = tile - tl * a.tiles_w;
-    const int cl = tl * kTileL + (b >> 3), cw = tw * kTileW + (b & 7);
-    const bool valid = pair_ok && cl < a.L && cw < a.W;
-    const int cell = valid ? cl * a.W + cw : 0;
-    const float *P = a.g.calibs + (size_t)view * 12;
+    const TileLane ln = tile_lane(a.n_views, a.n_tiles, a.tiles_w, a.L, a.W);
+    const float *P = a.g.calibs + (size_t)ln.view * 12;
     int shift = 0;
     for (int layer = 0; layer < a.nl; ++layer) {
-        const float gx = a.g.grid[cell * 3 + 0] + 0.0f, gy = a.g.grid[cell * 3 + 1] + 0.0f, gz = a.g.grid[cell * 3 + 2] + a.g.z_layers[layer];
-        float l = 0.0f, t = 0.0f, r = 0.0f, bt = 0.0f;
-#pragma unroll 1
-        for (int k = 0; k < 8; ++k) {
-            float nu, nv;
-            project_corner(a.g, P, gx, gy, gz, k, nu, nv);
-            if (k == 0) { l = r = nu; t = bt = nv; }
-            else { l = min_t(l, nu); r = max_t(r, nu); t = min_t(t, nv); bt = max_t(bt, nv); }
-        }
+        float l, t, r, bt;
+        cube_box(a.g, P, ln.cell, layer, l, t, r, bt);
         const float area = box_area(l, t, r, bt, a.Hf, a.Wf);
-        if (valid && box_visible(area, a.Hf, a.Wf)) shift = max(shift, sliver_shift(area, a.Hf, a.Wf));
+        if (ln.valid && box_visible(area, a.Hf, a.Wf)) shift = max(shift, sliver_shift(area, a.Hf, a.Wf));
     }
 #pragma unroll
     for (int m = 1; m < 32; m <<= 1) shift = max(shift, __shfl_xor(shift, m, 32));
     if (a.per_item) {
-        if (valid) a.out[(size_t)view * a.L * a.W + cell] = (unsigned char)shift;
-    } else if (pair_ok && b == 0 && shift > 0) {
-        atomicMax(a.tile_max + tile, (unsigned)shift);
+        if (ln.valid) a.out[(size_t)ln.view * a.L * a.W + ln.cell] = (unsigned char)shift;
+    } else if (ln.pair_ok && ln.b == 0 && shift > 0) {
+        atomicMax(a.tile_max + ln.tile, (unsigned)shift);
     }
 }
 __global__ __launch_bounds__(256) void sliver_expand_kernel(const unsigned *tile_max, unsigned char *out, int L, int W, int tiles_w)
@@ -342,8 +267,6 @@ __device__ __forceinline__ void split_block(const SplitArgs &sa, int b, unsigned
 // above the mean on the bench frame (4.9 tiles of ~18 items per workgroup), equal item counts 7 %.  A tile cut this way is
 // finished by the workgroup that holds its beginning, which gets the partial sums of the other one through the workspace (see
 // `flush`).  One workgroup, an LDS scan over per-thread sums.
-constexpr int kChunks = 8192; // (fine enough that a launch with any number of workgroups gets pieces within 3 % of each other)
-constexpr int kMaxBlocks = 512; // workgroups of the persistent kernel
 struct ChunkArgs {
     const unsigned *live[kMaxScales], *overflow[kMaxScales];
     const unsigned short *item_w; // (n_tiles, kMaxScales, views_pad): written by frame_records_kernel
@@ -518,24 +441,6 @@ constexpr int kDbgNoFills = 1, kDbgNoPool = 2, kDbgNoMfma = 4, kDbgOneW = 8, kDb
 // masked value -- instead of the map: what tests/test_fused_frame.py compares with the reference's voxel features.
 constexpr int kDbgDumpVox = 0x1000; // (set by VFA_FLAG_DUMP_VOX; bits 0-11 are VFA_FLAG_DEBUG's)
 
-struct Frag { bf16x8 hi, lo; };
-
-__device__ __forceinline__ float relu_t(float x) { return (x < 0.0f) ? 0.0f : x; } // NaN stays NaN
-
-__device__ __forceinline__ float4 mul4(float4 a, float w) { return make_float4(a.x * w, a.y * w, a.z * w, a.w * w); }
-__device__ __forceinline__ float4 fma4(float4 a, float w, float4 c)
-{
-    return make_float4(fmaf(a.x, w, c.x), fmaf(a.y, w, c.y), fmaf(a.z, w, c.z), fmaf(a.w, w, c.w));
-}
-// bilinear sample from the four rounded weights, taps in the order nw, ne, sw, se: one product, three FMAs
-__device__ __forceinline__ float4 sample4(float4 nw, float4 ne, float4 sw, float4 se, float w0, float w1, float w2, float w3)
-{
-    float4 v = mul4(nw, w0);
-    v = fma4(ne, w1, v);
-    v = fma4(sw, w2, v);
-    v = fma4(se, w3, v);
-    return v;
-}
 // Pooling layout: a wave owns four boxes of the tile and pools them SIDE BY SIDE -- 16 lanes x float4 = 64 channels of one
 // box, four boxes per wave instruction, four channel quarters per item.  Box parameters are per-lane registers (the box
 // record, read from the LDS slots behind the tap window, where LDS-DMA put it), control flow is the same for every box (always 16 taps: the
@@ -1496,7 +1401,6 @@ __global__ __launch_bounds__(512) void pool_rows_kernel(RowsArgs a)
     }
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct WorkspaceLayout {
     size_t live[kMaxScales], direct[kMaxScales], overflow[kMaxScales], counter, hdrs[kMaxScales], recs[kMaxScales], wfrag[kMaxScales],

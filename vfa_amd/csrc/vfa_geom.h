@@ -25,6 +25,7 @@ __device__ __forceinline__ float clamp_t(float v, float lo, float hi)
 }
 __device__ __forceinline__ float min_t(float a, float b) { return (a != a || a < b) ? a : b; }
 __device__ __forceinline__ float max_t(float a, float b) { return (a != a || a > b) ? a : b; }
+__device__ __forceinline__ float relu_t(float x) { return (x < 0.0f) ? 0.0f : x; } // NaN stays NaN
 
 __device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
@@ -104,6 +105,59 @@ __device__ __forceinline__ void project_corner_ex(const BoxGeom &g, const float 
     const float u = h[0] / h[2], w = h[1] / h[2];
     nu_pre = (2.0f * u) / g.img_w; nu_pre = nu_pre - 1.0f; nu = clamp_t(nu_pre, g.cmin, g.cmax);
     nv_pre = (2.0f * w) / g.img_h; nv_pre = nv_pre - 1.0f; nv = clamp_t(nv_pre, g.cmin, g.cmax);
+}
+
+// The point the corner offsets of the cube of (cell, layer) are added to.
+__device__ __forceinline__ void cube_origin(const BoxGeom &g, int cell, int layer, float &gx, float &gy, float &gz)
+{
+    gx = g.grid[cell * 3 + 0] + 0.0f; // + the int64 zeros of z_corners (vfa_op.py:52, :64)
+    gy = g.grid[cell * 3 + 1] + 0.0f;
+    gz = g.grid[cell * 3 + 2] + g.z_layers[layer];
+}
+
+// The image box of the cube of (cell, layer) seen by `P`: min / max of its eight corners in corner order (k == 0 initialises) --
+// THE statement of the frame's box geometry: every forward kernel, the records of both frame kernels and the sliver shifts of the
+// training backward take l, t, r, b from here, so they agree bit for bit by construction.
+// UNROLL: the eight corners as straight-line code (true) or as a rolled loop (false: the kernels that have no registers to spare).
+template <bool UNROLL = false>
+__device__ __forceinline__ void cube_box(const BoxGeom &g, const float *__restrict__ P, int cell, int layer, float &l, float &t,
+                                         float &r, float &b)
+{
+    float gx, gy, gz;
+    cube_origin(g, cell, layer, gx, gy, gz);
+    l = t = r = b = 0.0f;
+    auto corner = [&](int k) {
+        float nu, nv;
+        project_corner(g, P, gx, gy, gz, k, nu, nv);
+        if (k == 0) { l = r = nu; t = b = nv; }
+        else { l = min_t(l, nu); r = max_t(r, nu); t = min_t(t, nv); b = max_t(b, nv); }
+    };
+    if constexpr (UNROLL) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) corner(k);
+    } else {
+#pragma unroll 1
+        for (int k = 0; k < 8; ++k) corner(k);
+    }
+}
+
+// The same box with one corner per lane: lanes 8 j .. 8 j + 7 hold the corners of one cube (corner = lane & 7), every lane leaves
+// with the box.  min / max are exact and order-insensitive (NaN propagates either way): bit for bit `cube_box`.
+__device__ __forceinline__ void cube_box_lanes(const BoxGeom &g, const float *__restrict__ P, int cell, int layer, int corner,
+                                               float &l, float &t, float &r, float &b)
+{
+    float gx, gy, gz;
+    cube_origin(g, cell, layer, gx, gy, gz);
+    float nu, nv;
+    project_corner(g, P, gx, gy, gz, corner, nu, nv);
+    l = r = nu; t = b = nv;
+#pragma unroll
+    for (int m = 1; m < 8; m <<= 1) {
+        l = min_t(l, __shfl_xor(l, m));
+        r = max_t(r, __shfl_xor(r, m));
+        t = min_t(t, __shfl_xor(t, m));
+        b = max_t(b, __shfl_xor(b, m));
+    }
 }
 
 __device__ __forceinline__ float box_area(float l, float t, float r, float b, int Hf, int Wf)

@@ -181,18 +181,8 @@ __global__ __launch_bounds__(256) void box_params_kernel(BoxGeom g, int n_cells,
     const int cell = (int)(idx % n_cells);
     const size_t vl = idx / n_cells;
     const int layer = (int)(vl % nl), view = (int)(vl / nl);
-    const float *P = g.calibs + (size_t)view * 12;
-    const float gx = g.grid[cell * 3 + 0] + 0.0f; // + the int64 zeros of z_corners (vfa_op.py:52, :64)
-    const float gy = g.grid[cell * 3 + 1] + 0.0f;
-    const float gz = g.grid[cell * 3 + 2] + g.z_layers[layer];
-    float l = 0, t = 0, r = 0, b = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        float nu, nv;
-        project_corner(g, P, gx, gy, gz, k, nu, nv);
-        if (k == 0) { l = r = nu; t = b = nv; }
-        else { l = min_t(l, nu); r = max_t(r, nu); t = min_t(t, nv); b = max_t(b, nv); }
-    }
+    float l, t, r, b;
+    cube_box<true>(g, g.calibs + (size_t)view * 12, cell, layer, l, t, r, b);
     const float a = box_area(l, t, r, b, Hf, Wf);
     box[idx] = make_float4(l, t, r, b);
     area[idx] = a;
@@ -405,18 +395,7 @@ __device__ __forceinline__ void stage_box_records(BoxRec *recs, long long tile0,
         float l, t, r, b, area;
         bool vis;
         if constexpr (FUSED) {
-            const float *P = g.calibs + (size_t)view * 12;
-            const float gx = g.grid[cell * 3 + 0] + 0.0f; // + the int64 zeros of z_corners (vfa_op.py:52, :64)
-            const float gy = g.grid[cell * 3 + 1] + 0.0f;
-            const float gz = g.grid[cell * 3 + 2] + g.z_layers[layer];
-            l = t = r = b = 0.0f;
-#pragma unroll 1
-            for (int k = 0; k < 8; ++k) {
-                float nu, nv;
-                project_corner(g, P, gx, gy, gz, k, nu, nv);
-                if (k == 0) { l = r = nu; t = b = nv; }
-                else { l = min_t(l, nu); r = max_t(r, nu); t = min_t(t, nv); b = max_t(b, nv); }
-            }
+            cube_box(g, g.calibs + (size_t)view * 12, cell, layer, l, t, r, b);
             area = box_area(l, t, r, b, d.Hf, d.Wf);
             vis = box_visible(area, d.Hf, d.Wf);
         } else {
@@ -605,20 +584,7 @@ __global__ __launch_bounds__(kWave) void gather_cached_kernel(const float *__res
     bool vis = false;
     {
         const int cell = d.cell_begin + cell0 + (valid ? b : 0);
-        const float *P = g.calibs + (size_t)view * 12;
-        const float gx = g.grid[cell * 3 + 0] + 0.0f; // + the int64 zeros of z_corners (vfa_op.py:52, :64)
-        const float gy = g.grid[cell * 3 + 1] + 0.0f;
-        const float gz = g.grid[cell * 3 + 2] + g.z_layers[layer];
-        float nu, nv;
-        project_corner(g, P, gx, gy, gz, corner, nu, nv);
-        l = r = nu; t = bt = nv;
-#pragma unroll
-        for (int m = 1; m < 8; m <<= 1) { // exact, order-insensitive (NaN propagates either way)
-            l = min_t(l, __shfl_xor(l, m));
-            r = max_t(r, __shfl_xor(r, m));
-            t = min_t(t, __shfl_xor(t, m));
-            bt = max_t(bt, __shfl_xor(bt, m));
-        }
+        cube_box_lanes(g, g.calibs + (size_t)view * 12, cell, layer, corner, l, t, r, bt);
         area = box_area(l, t, r, bt, d.Hf, d.Wf);
         vis = valid && box_visible(area, d.Hf, d.Wf);
     }
@@ -834,20 +800,7 @@ __device__ __forceinline__ bool gather_backward_tile(BackwardLds &L, const BoxGe
         bool vis = false;
         {
             const int cell = d.cell_begin + (int)(valid ? lc : 0);
-            const float *P = g.calibs + (size_t)view * 12;
-            const float gx = g.grid[cell * 3 + 0] + 0.0f; // + the int64 zeros of z_corners (vfa_op.py:52, :64)
-            const float gy = g.grid[cell * 3 + 1] + 0.0f;
-            const float gz = g.grid[cell * 3 + 2] + g.z_layers[layer];
-            float nu, nv;
-            project_corner(g, P, gx, gy, gz, corner, nu, nv);
-            l = r = nu; t = bt = nv;
-#pragma unroll
-            for (int m = 1; m < 8; m <<= 1) { // exact, order-insensitive (NaN propagates either way)
-                l = min_t(l, __shfl_xor(l, m));
-                r = max_t(r, __shfl_xor(r, m));
-                t = min_t(t, __shfl_xor(t, m));
-                bt = max_t(bt, __shfl_xor(bt, m));
-            }
+            cube_box_lanes(g, g.calibs + (size_t)view * 12, cell, layer, corner, l, t, r, bt);
             area = box_area(l, t, r, bt, d.Hf, d.Wf);
             vis = valid && box_visible(area, d.Hf, d.Wf);
         }
@@ -1237,17 +1190,7 @@ __global__ __launch_bounds__(64 * (4 + kProducers)) void fused_collapse_kernel(c
             float l = 0.f, t = 0.f, r = 0.f, b = 0.f, area = 0.f;
             bool vis = false;
             if (valid) {
-                const float *P = g.calibs + (size_t)view * 12;
-                const float gx = g.grid[cell * 3 + 0] + 0.0f;
-                const float gy = g.grid[cell * 3 + 1] + 0.0f;
-                const float gz = g.grid[cell * 3 + 2] + g.z_layers[layer];
-#pragma unroll 1
-                for (int k = 0; k < 8; ++k) {
-                    float nu, nv;
-                    project_corner(g, P, gx, gy, gz, k, nu, nv);
-                    if (k == 0) { l = r = nu; t = b = nv; }
-                    else { l = min_t(l, nu); r = max_t(r, nu); t = min_t(t, nv); b = max_t(b, nv); }
-                }
+                cube_box(g, g.calibs + (size_t)view * 12, cell, layer, l, t, r, b);
                 area = box_area(l, t, r, b, fd.Hf, fd.Wf);
                 vis = box_visible(area, fd.Hf, fd.Wf);
             }
@@ -1566,8 +1509,6 @@ __global__ __launch_bounds__(kWave) void integral_rows_backward_kernel(const flo
 // ------------------------------------------------------------------------------------------------
 // collapse epilogues                                            reference vfa_op.py:124; vfanet.py:79, 82
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float relu_t(float x) { return (x < 0.0f) ? 0.0f : x; } // NaN stays NaN
-
 template <int VEC>
 __global__ __launch_bounds__(256) void bias_relu_accumulate_kernel(const float *__restrict__ lin,
                                                                    const float *__restrict__ bias,

@@ -33,6 +33,7 @@
 #include "vfa_geom.h"
 #include "vfa_pipe_seq.h"
 #include "vfa_split.h"
+#include "vfa_tile.h"
 
 #ifndef VFA_TICKET_ORDER
 // The hand-off ticket of a run cut between workgroups (finish_run): a RELAXED agent-scope add.  Every byte handed off is stored `sc1`
@@ -49,12 +50,8 @@ namespace {
 using namespace vfa_dev;
 using namespace vfa_pipe;
 
-constexpr int kTileW = 8, kTileL = 4, kTileBoxes = kTileW * kTileL;
-constexpr int kC = 256;
-constexpr int kRecBytes = 48, kHdrBytes = 32; // (box record: see pipe_records_kernel)
-constexpr int kMaxScales = 3;
-constexpr int kSlotBytes = kC * 4;              // one tap in the integral image: 256 fp32
-constexpr int kQSlot = 256;                     // ... and the 64-channel quarter of it that a step needs
+constexpr int kRecBytes = 48;                   // (vfa_fused.hip: 96 -- box record: see pipe_records_kernel)
+constexpr int kQSlot = 256;                     // the 64-channel quarter of a tap (kSlotBytes) that a step needs
 constexpr int kWinSlots = 112;                  // LDS tap window of a (tile, view, layer, scale), in quarter slots: four of them (two being
                                                 // pooled, two arriving); 28 KiB each.  A multiple of 4: a fill instruction brings four
 constexpr int kWinSlots3 = 96;                   // ... of the three-piece variant (VFA_FLAG_TERMS 6): a third bf16 plane takes 17 KiB of LDS
@@ -78,7 +75,6 @@ constexpr int kChunkStride = kStepRows * 16 + 32;
 constexpr int kPlaneBytes = 8 * kChunkStride;   // 8448
 constexpr int kWPlanes = 3;                     // bf16 planes of the split collapse weight in the workspace: hi, mid (= lo of the two-piece split), lo
 constexpr int kSteps = 16;                      // k-steps of v_mfma_f32_32x32x16_bf16 per layer
-constexpr int kChunks = 8192, kMaxBlocks = 512;
 // Balance state of a workspace (written by vfa_pipe_balance_f32, read by the frame kernel; nothing else touches it):
 //   int bounds[kMaxBlocks + 1]   workgroup wg of a launch of `tag` workgroups takes the pieces [bounds[wg], bounds[wg + 1]) of the kChunks
 //   int tag                      number of workgroups the bounds are for (0: none -- the uniform split)
@@ -93,8 +89,6 @@ constexpr int kMetaMagic = 0x56464142;
 // batched frames: binary places by which the fp16 split of one frame may lie below the launch's (pipe_frame_exp_kernel); with the
 // largest sliver shift (48) the sub-tile's factor 2^-(shift + dea) stays a normal fp32 power of two
 constexpr int kMaxFrameDea = 126 - 48;
-constexpr int kVis = 1;
-constexpr int kTileLive = 1, kTileDirect = 2;
 // VFA_FLAG_DUMP_VOX (diagnostic build): with ONE view, ONE scale and ONE layer `out` receives the pooled fp32 voxel features (cell,
 // channel) exactly as the pooling waves form them in front of the operand split, instead of the map (tests/test_pipe_frame.py)
 constexpr int kDbgDumpVox = 0x1000; // (set by VFA_FLAG_DUMP_VOX; bits 0-11 are VFA_FLAG_DEBUG's)
@@ -112,13 +106,6 @@ constexpr int kDbgDumpVox = 0x1000; // (set by VFA_FLAG_DUMP_VOX; bits 0-11 are 
 #define VFA_PIPE_PRIO_MAT 0
 #endif
 constexpr int kAblate = VFA_PIPE_ABLATE;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-struct ScaleDims { int Hf, Wf; };
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-__device__ __forceinline__ float relu_t(float x) { return (x < 0.0f) ? 0.0f : x; } // NaN stays NaN
 
 // ------------------------------------------------------------------------------------------------
 // 1. geometry of the frame: one half-wave per (view, tile), lane = cell of the tile; every z-layer, every scale
@@ -144,37 +131,17 @@ __global__ __launch_bounds__(kWave) void pipe_records_kernel(RecordArgs a)
     // 84 us; a half-wave per (view, tile, layer, SCALE) was slower again (107: 41 000 one-wave workgroups), and so was writing the
     // records without the LDS staging (85, and the integral images beside it 93 instead of 84))
     __shared__ uint4 stage[2][kTileBoxes * 3];
-    const int lane = threadIdx.x, half = lane >> 5, b = lane & 31;
-    const long long unit = (long long)blockIdx.x * 2 + half;
-    const long long pair = unit / a.nl;
-    const int layer0 = (int)(unit - pair * a.nl);
-    const bool pair_ok = pair < (long long)a.n_views * a.n_tiles;
-    const int view = pair_ok ? (int)(pair / a.n_tiles) : 0, tile = pair_ok ? (int)(pair % a.n_tiles) : 0;
-    const int tl = tile / a.tiles_w, tw = tile - tl * a.tiles_w;
-    const int cl = tl * kTileL + (b >> 3), cw = tw * kTileW + (b & 7);
-    const bool valid = pair_ok && cl < a.L && cw < a.W;
-    const int cell = valid ? cl * a.W + cw : 0;
+    const TileLane ln = tile_lane(a.n_views, a.n_tiles, a.tiles_w, a.L, a.W, a.nl);
+    const int half = ln.half, b = ln.b, view = ln.view, tile = ln.tile, layer = ln.layer, cell = ln.cell;
+    const bool pair_ok = ln.pair_ok, valid = ln.valid;
     const float *P = a.g.calibs + (size_t)view * 12;
-    const float g0 = a.g.grid[cell * 3 + 0], g1 = a.g.grid[cell * 3 + 1], g2 = a.g.grid[cell * 3 + 2];
     bool live_any[kMaxScales] = {false, false, false};
     int shift_max[kMaxScales] = {0, 0, 0};
     unsigned n_glob = 0;
     {
-        const int layer = layer0;
         // the cube once per (view, cell, layer): scale-independent                     vfa_op.py:64-88, utils.py:56-59
         float l, t, r, bt;
-        {
-            const float gx = g0 + 0.0f, gy = g1 + 0.0f; // + the int64 zeros of z_corners (vfa_op.py:52, :64)
-            const float gz = g2 + a.g.z_layers[layer];
-            l = t = r = bt = 0.0f;
-#pragma unroll 1
-            for (int k = 0; k < 8; ++k) {
-                float nu, nv;
-                project_corner(a.g, P, gx, gy, gz, k, nu, nv);
-                if (k == 0) { l = r = nu; t = bt = nv; }
-                else { l = min_t(l, nu); r = max_t(r, nu); t = min_t(t, nv); bt = max_t(bt, nv); }
-            }
-        }
+        cube_box(a.g, P, cell, layer, l, t, r, bt);
         const size_t item = ((size_t)tile * a.nl + layer) * a.n_views + view;
 #pragma unroll 1
         for (int s = 0; s < a.n_scales; ++s) {
@@ -183,10 +150,11 @@ __global__ __launch_bounds__(kWave) void pipe_records_kernel(RecordArgs a)
             const bool vis = valid && box_visible(area, Hf, Wf);                                  // :106
             const float masked = valid ? area * 0.0f : 0.0f; // value of a masked voxel: 0, or NaN when the box itself is NaN
             const bool live_box = vis || (valid && masked != masked);
-            const Axis xl = make_axis(l, Wf), xr = make_axis(r, Wf), yt = make_axis(t, Hf), yb = make_axis(bt, Hf);
-            // tap coordinates, out-of-image taps redirected to the zero border (coordinate -1 or Hf / Wf)
-            const int xs[4] = {clampi(xl.i0, -1, Wf), clampi(xl.i0 + 1, -1, Wf), clampi(xr.i0, -1, Wf), clampi(xr.i0 + 1, -1, Wf)};
-            const int ys[4] = {clampi(yt.i0, -1, Hf), clampi(yt.i0 + 1, -1, Hf), clampi(yb.i0, -1, Hf), clampi(yb.i0 + 1, -1, Hf)};
+            // The taps as locals and the half-wave reduction spelled out (vfa_fused.hip: tile_window, tap_parts): this kernel sits at 72
+            // registers, the last count with seven waves per SIMD, and through the shared helpers the compiler needs 74.
+            const BoxTaps tp = box_taps(l, t, r, bt, Hf, Wf);
+            const Axis xl = tp.xl, xr = tp.xr, yt = tp.yt, yb = tp.yb;
+            const int xs[4] = {tp.xs[0], tp.xs[1], tp.xs[2], tp.xs[3]}, ys[4] = {tp.ys[0], tp.ys[1], tp.ys[2], tp.ys[3]};
             // window of the tile over its VISIBLE boxes: columns [x0, x1], top rows [t0, t1], bottom rows [b0, b1]
             constexpr int kBig = 1 << 20;
             int x0 = vis ? min(xs[0], xs[2]) : kBig, x1 = vis ? max(xs[1], xs[3]) : -kBig;
@@ -203,28 +171,16 @@ __global__ __launch_bounds__(kWave) void pipe_records_kernel(RecordArgs a)
             const unsigned long long vis_all = __ballot(vis), live_all = __ballot(live_box);
             const bool any_vis = ((vis_all >> (32 * half)) & 0xffffffffull) != 0ull;
             const bool any_live = ((live_all >> (32 * half)) & 0xffffffffull) != 0ull;
-            int cwid = 0, top_rows = 0, bot_rows = 0, n_slots = 0;
-            if (any_vis) {
-                cwid = x1 - x0 + 1;
-                if (b0 <= t1 + 1) { // the bands touch or overlap: one band [t0, max(t1, b1)]
-                    top_rows = max(t1, b1) - t0 + 1;
-                    bot_rows = 0;
-                    b0 = t0 + top_rows;
-                } else {
-                    top_rows = t1 - t0 + 1;
-                    bot_rows = b1 - b0 + 1;
-                }
-                n_slots = cwid * (top_rows + bot_rows);
-            }
+            const Window win = make_window(any_vis, x0, x1, t0, t1, b0, b1);
+            const int n_slots = win.n_slots;
             // pooled straight from the integral image (pixel coordinates in the record): the window does not fit, or the padded
             // image has 2^24 pixels or more (the window fetch of the frame kernel works out its addresses with 24-bit multiplies)
             const bool direct = n_slots > a.win_slots || (long long)(Hf + 2) * (Wf + 2) >= (1ll << 24);
-            auto slot_row = [&](int y) { return y < t0 + top_rows ? y - t0 : top_rows + (y - b0); };
             unsigned rows[4], cols[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (direct) { rows[k] = (unsigned)(ys[k] + 1); cols[k] = (unsigned)(xs[k] + 1); }
-                else { rows[k] = (unsigned)(slot_row(ys[k]) * cwid); cols[k] = (unsigned)(xs[k] - x0); }
+                else { rows[k] = (unsigned)(slot_row(win, ys[k]) * win.cwid); cols[k] = (unsigned)(xs[k] - win.x0); }
             }
             // A box in 48 bytes: the upper bilinear fractions of its four axes (the sixteen tap weights are products of them and of
             // 1 - them: `unpack` of the frame kernel forms them with the same two rounded operations as `bilinear_weights`), the factor
@@ -244,10 +200,9 @@ __global__ __launch_bounds__(kWave) void pipe_records_kernel(RecordArgs a)
                 for (int k = 0; k < 3; ++k) rec[k * 32 + b] = stage[half][k * 32 + b];
                 if (b == 0) {
                     uint4 *hdr = reinterpret_cast<uint4 *>(a.hdrs[s] + item * kHdrBytes);
-                    const int inv = cwid > 0 ? (65536 + cwid - 1) / cwid : 0; // floor(s / cwid) == (s * inv) >> 16 for s < 128
                     const unsigned hflags = (any_live ? kTileLive : 0) | (direct ? kTileDirect : 0);
-                    hdr[0] = make_uint4(hflags, (unsigned)n_slots, (unsigned)cwid, (unsigned)inv);
-                    hdr[1] = make_uint4((unsigned)x0, (unsigned)t0, (unsigned)top_rows, (unsigned)b0);
+                    hdr[0] = tile_header0(hflags, win, (unsigned)win.cwid);
+                    hdr[1] = tile_header1(win);
                 }
             }
             live_any[s] = live_any[s] || any_live;
@@ -520,23 +475,7 @@ struct DevMasks {
     }
 };
 
-struct Frag { bf16x8 hi, lo; };
 struct Frag3 { bf16x8 hi, lo, lo2; };
-
-__device__ __forceinline__ float4 mul4(float4 a, float w) { return make_float4(a.x * w, a.y * w, a.z * w, a.w * w); }
-__device__ __forceinline__ float4 fma4(float4 a, float w, float4 c)
-{
-    return make_float4(fmaf(a.x, w, c.x), fmaf(a.y, w, c.y), fmaf(a.z, w, c.z), fmaf(a.w, w, c.w));
-}
-// bilinear sample from the four rounded weights, taps in the order nw, ne, sw, se: one product, three FMAs
-__device__ __forceinline__ float4 sample4(float4 nw, float4 ne, float4 sw, float4 se, float w0, float w1, float w2, float w3)
-{
-    float4 v = mul4(nw, w0);
-    v = fma4(ne, w1, v);
-    v = fma4(sw, w2, v);
-    v = fma4(se, w3, v);
-    return v;
-}
 
 // Tap reads of the pooling waves, by hand: four 16-byte taps (one corner of the box) per instruction group, counted waits.  Eight
 // taps are in flight at most -- a corner's registers take the corner after the next once it is consumed --: 32 tap registers
@@ -2012,7 +1951,6 @@ inline int pipe_blocks(int n_tiles, int reserved_cus)
     return nblk > kMaxBlocks ? kMaxBlocks : nblk;
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct PipeLayout {
     size_t live[kMaxScales], shifts[kMaxScales], subcost[kMaxScales], tickets, globs, masks_bytes, hdrs[kMaxScales], recs[kMaxScales], wfrag[kMaxScales], chunks, ranks, costs, partial, slots, diag, balance, wmax, wexp, amax, meta, fdea, total;

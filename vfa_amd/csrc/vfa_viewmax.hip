@@ -16,14 +16,13 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "vfa_hip.h"
+#include "vfa_geom.h"
 
 namespace {
+using vfa_dev::relu_t;
 
 constexpr int kMaxAhead = 4;       // cameras whose three lin rows a forward thread loads before it compares
 constexpr int kMaxViews = 256;     // the winner index is one byte
-
-__device__ __forceinline__ float relu_t(float x) { return (x < 0.0f) ? 0.0f : x; } // NaN stays NaN
 
 // vfanet.py:79 for one element, in the reference's association order
 __device__ __forceinline__ float scale_sum(float x8, float x16, float x32, float c8, float c16, float c32)

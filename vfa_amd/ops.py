@@ -306,11 +306,29 @@ def lateral_conv_backward(dzs, ys, means, feats, weights, workspaces, want_feat=
     return g_f, g_w
 
 
+def _geometry(calibs, grid, z_layers, corner_off, flat=False):
+    """The geometry operands as the kernels read them, contiguous fp32 on the device: calibs (n, 12), grid (L, W, 3) -- (cells, 3)
+    with ``flat`` --, z_layers (nl), corner_off (8, 3)."""
+    _lib.require_device(calibs, grid, z_layers, corner_off)
+    grid = grid.reshape(-1, 3) if flat else grid.reshape(grid.shape[-3], grid.shape[-2], 3)
+    return _f32c(calibs.reshape(-1, 12)), _f32c(grid), _f32c(z_layers.reshape(-1)), _f32c(corner_off.reshape(8, 3))
+
+
+def _weight_ptrs(weights, n_scales, shape):
+    """Host array of the device pointers of one ``collapse.weight`` of ``shape`` per scale (None -> None)."""
+    if weights is None:
+        return None
+    weights = [_f32c(w) for w in weights]
+    assert len(weights) == n_scales and all(tuple(w.shape) == shape for w in weights)
+    _lib.require_device(*weights)
+    ptrs = _lib.ptr_array(weights)
+    ptrs.tensors = weights  # (raw pointers: a converted copy has to live as long as they do)
+    return ptrs
+
+
 def box_params(calibs, grid_flat, z_layers, corner_off, conv_kind, image_wh, feat_hw, crange=(-1, 0.95)):
     """-> box (n,nl,cells,4), area (n,nl,cells), visible (n,nl,cells) uint8 (reference vfa_op.py:64-106)."""
-    _lib.require_device(calibs, grid_flat, z_layers, corner_off)
-    calibs = _f32c(calibs.reshape(-1, 12))
-    grid_flat, z_layers, corner_off = _f32c(grid_flat.reshape(-1, 3)), _f32c(z_layers), _f32c(corner_off.reshape(8, 3))
+    calibs, grid_flat, z_layers, corner_off = _geometry(calibs, grid_flat, z_layers, corner_off, flat=True)
     n, n_cells, nl = calibs.shape[0], grid_flat.shape[0], z_layers.numel()
     dev = calibs.device
     box = torch.empty((n, nl, n_cells, 4), dtype=torch.float32, device=dev)
@@ -800,12 +818,8 @@ def sliver_shifts(calibs, grid, z_layers, corner_off, conv_kind, image_wh, feat_
     """The sliver shifts of a frame per output row of the collapse product (``vfa_sliver_shifts_u8``): uint8 (n_views, L*W) for the
     serial frame kernel's items (``per_item`` True: single-layer grids, one scale) or (1, L*W) for the pipelined kernel's (tile, scale)
     over all views and layers -- what ``collapse_gemm_relu_backward(..., absmax=..., shift=...)`` needs to repeat the forward's scaling."""
-    _lib.require_device(calibs, grid, z_layers, corner_off)
-    grid = _f32c(grid.reshape(grid.shape[-3], grid.shape[-2], 3))
-    L, W = grid.shape[:2]
-    calibs = _f32c(calibs.reshape(-1, 12))
-    n = calibs.shape[0]
-    z_layers, corner_off = _f32c(z_layers.reshape(-1)), _f32c(corner_off.reshape(8, 3))
+    calibs, grid, z_layers, corner_off = _geometry(calibs, grid, z_layers, corner_off)
+    n, (L, W) = calibs.shape[0], grid.shape[:2]
     out = torch.empty((n if per_item else 1, L * W), dtype=torch.uint8, device=calibs.device)
     need = _lib.lib().vfa_sliver_shifts_scratch_bytes(L, W)
     scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=calibs.device)
@@ -823,12 +837,8 @@ def frame_records(calibs, grid, z_layers, corner_off, conv_kind, image_wh, feat_
     calibs (n,3,4), grid (L,W,3) or (1,L,W,3), feat_hws = [(Hf,Wf), ...] (1..3 scales), weights = one (256,256) per scale.
     ``cuts=False``: only the boxes (``vfa_frame_boxes_f32``: what the pre-pass of ``pool_collapse`` needs); ``frame_cuts`` then
     adds the work cuts and the weight split."""
-    _lib.require_device(calibs, grid, z_layers, corner_off)
-    grid = _f32c(grid.reshape(grid.shape[-3], grid.shape[-2], 3))
-    L, W = grid.shape[:2]
-    calibs = _f32c(calibs.reshape(-1, 12))
-    n = calibs.shape[0]
-    z_layers, corner_off = _f32c(z_layers), _f32c(corner_off.reshape(8, 3))
+    calibs, grid, z_layers, corner_off = _geometry(calibs, grid, z_layers, corner_off)
+    n, (L, W) = calibs.shape[0], grid.shape[:2]
     if z_layers.numel() != 1:
         raise _lib.VFAHipError("frame_records / pool_collapse cover single-layer grids (nl = 1) only")
     ns = len(feat_hws)
@@ -840,12 +850,7 @@ def frame_records(calibs, grid, z_layers, corner_off, conv_kind, image_wh, feat_
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=calibs.device)
     hw = _lib.int_array([v for f in feat_hws for v in f])
-    wts = None
-    if weights is not None:
-        weights = [_f32c(w) for w in weights]
-        assert len(weights) == ns and all(tuple(w.shape) == (256, 256) for w in weights)
-        _lib.require_device(*weights)
-        wts = _lib.ptr_array(weights)
+    wts = _weight_ptrs(weights, ns, (256, 256))
     if not cuts:
         _launch("vfa_frame_boxes_f32", _lib.ptr(calibs), _lib.ptr(grid), _lib.ptr(z_layers), _lib.ptr(corner_off), n, L, W,
                 int(conv_kind), float(image_wh[0]), float(image_wh[1]), float(crange[0]), float(crange[1]), ns, hw,
@@ -860,12 +865,7 @@ def frame_records(calibs, grid, z_layers, corner_off, conv_kind, image_wh, feat_
 def frame_cuts(workspace, n_views, grid_lw, n_scales, weights=None, terms=0):
     """Second half of ``frame_records(..., cuts=False)``: the work cuts of the persistent kernel + the split collapse weights."""
     _lib.require_device(workspace)
-    wts = None
-    if weights is not None:
-        weights = [_f32c(w) for w in weights]
-        assert len(weights) == n_scales and all(tuple(w.shape) == (256, 256) for w in weights)
-        _lib.require_device(*weights)
-        wts = _lib.ptr_array(weights)
+    wts = _weight_ptrs(weights, n_scales, (256, 256))
     _launch("vfa_frame_cuts_f32", int(n_views), int(grid_lw[0]), int(grid_lw[1]), int(n_scales), wts, int(terms) & 0xf, _lib.ptr(workspace),
             workspace.numel(), _lib.current_stream_handle(), tag=(int(n_views), int(grid_lw[0]), int(grid_lw[1]), int(n_scales)))
     return workspace
@@ -947,12 +947,8 @@ def pipe_records(calibs, grid, z_layers, corner_off, conv_kind, image_wh, feat_h
     (256, 256*nl) per scale in the REFERENCE column order c*nl + layer (``collapse.weight`` as it is).  ``cuts=False``: the
     boxes only (``pipe_cuts`` adds the rest).  ``terms``: the product variant ``pipe_collapse`` will be called with (6 = three bf16
     pieces per operand: smaller LDS tap windows, so the geometry has to know)."""
-    _lib.require_device(calibs, grid, z_layers, corner_off)
-    grid = _f32c(grid.reshape(grid.shape[-3], grid.shape[-2], 3))
-    L, W = grid.shape[:2]
-    calibs = _f32c(calibs.reshape(-1, 12))
-    n = calibs.shape[0]
-    z_layers, corner_off = _f32c(z_layers.reshape(-1)), _f32c(corner_off.reshape(8, 3))
+    calibs, grid, z_layers, corner_off = _geometry(calibs, grid, z_layers, corner_off)
+    n, (L, W) = calibs.shape[0], grid.shape[:2]
     nl, ns = z_layers.numel(), len(feat_hws)
     need = pipe_workspace_bytes(n, L, W, nl, ns)
     if workspace is None or workspace.numel() < need:
@@ -969,12 +965,7 @@ def pipe_records(calibs, grid, z_layers, corner_off, conv_kind, image_wh, feat_h
         _launch("vfa_pipe_boxes_f32", *args, int(terms) & 0xf, _lib.ptr(workspace), workspace.numel(), _lib.current_stream_handle(),
                 tag=(n, L, W, nl, ns))
         return workspace
-    wts = None
-    if weights is not None:
-        weights = [_f32c(w) for w in weights]
-        assert len(weights) == ns and all(tuple(w.shape) == (256, 256 * nl) for w in weights)
-        _lib.require_device(*weights)
-        wts = _lib.ptr_array(weights)
+    wts = _weight_ptrs(weights, ns, (256, 256 * nl))
     _launch("vfa_pipe_records_f32", *args, wts, int(terms) & 0xf, _lib.ptr(workspace), workspace.numel(), _lib.current_stream_handle(),
             tag=(n, L, W, nl, ns))
     return workspace
@@ -983,12 +974,7 @@ def pipe_records(calibs, grid, z_layers, corner_off, conv_kind, image_wh, feat_h
 def pipe_cuts(workspace, n_views, grid_lw, n_layers, n_scales, weights=None, terms=0):
     """Second half of ``pipe_records(..., cuts=False)``: the work cuts of the persistent kernel + the split collapse weights."""
     _lib.require_device(workspace)
-    wts = None
-    if weights is not None:
-        weights = [_f32c(w) for w in weights]
-        assert len(weights) == n_scales and all(tuple(w.shape) == (256, 256 * n_layers) for w in weights)
-        _lib.require_device(*weights)
-        wts = _lib.ptr_array(weights)
+    wts = _weight_ptrs(weights, n_scales, (256, 256 * n_layers))
     _launch("vfa_pipe_cuts_f32", int(n_views), int(grid_lw[0]), int(grid_lw[1]), int(n_layers), int(n_scales), wts, int(terms) & 0xf, _lib.ptr(workspace),
             workspace.numel(), _lib.current_stream_handle(), tag=(int(n_views), int(grid_lw[0]), int(grid_lw[1]), int(n_layers), int(n_scales)))
     return workspace
@@ -1073,12 +1059,8 @@ def pipe_batch_records(calibs, grid, z_layers, corner_off, conv_kind, image_wh, 
     """``pipe_records`` for a batch of ``n_frames`` frames of one static rig: the geometry once, the work cuts over the frames' virtual
     tiles and the batch record -> a workspace of exactly ``pipe_batch_workspace_bytes`` bytes (allocated when ``workspace`` is None,
     with a cleared balance state)."""
-    _lib.require_device(calibs, grid, z_layers, corner_off)
-    grid = _f32c(grid.reshape(grid.shape[-3], grid.shape[-2], 3))
-    L, W = grid.shape[:2]
-    calibs = _f32c(calibs.reshape(-1, 12))
-    n = calibs.shape[0]
-    z_layers, corner_off = _f32c(z_layers.reshape(-1)), _f32c(corner_off.reshape(8, 3))
+    calibs, grid, z_layers, corner_off = _geometry(calibs, grid, z_layers, corner_off)
+    n, (L, W) = calibs.shape[0], grid.shape[:2]
     nl, ns = z_layers.numel(), len(feat_hws)
     need = pipe_batch_workspace_bytes(n_frames, n, L, W, nl, ns)
     if workspace is None:
@@ -1086,12 +1068,7 @@ def pipe_batch_records(calibs, grid, z_layers, corner_off, conv_kind, image_wh, 
         if need > 0:
             bal = pipe_batch_workspace_layout(n_frames, n, L, W, nl, ns)["balance"]
             workspace[bal:bal + BALANCE_STATE_BYTES].zero_()
-    wts = None
-    if weights is not None:
-        weights = [_f32c(w) for w in weights]
-        assert len(weights) == ns and all(tuple(w.shape) == (256, 256 * nl) for w in weights)
-        _lib.require_device(*weights)
-        wts = _lib.ptr_array(weights)
+    wts = _weight_ptrs(weights, ns, (256, 256 * nl))
     hw = _lib.int_array([v for f in feat_hws for v in f])
     _launch("vfa_pipe_batch_records_f32", _lib.ptr(calibs), _lib.ptr(grid), _lib.ptr(z_layers), nl, _lib.ptr(corner_off), n, L, W,
             int(conv_kind), float(image_wh[0]), float(image_wh[1]), float(crange[0]), float(crange[1]), ns, hw, wts, int(n_frames),

@@ -161,16 +161,22 @@ def _unfused_terms(terms=None):
     return 3 if terms in (0, 2, 6) else terms
 
 
+def _one_frame_module_set(mods, n_views):
+    """One to three projector modules (one per feature scale) of 256 channels that share layer count, geometry, data set and image
+    size, for at most 32 cameras: the module sets the per-frame kernels are built for."""
+    m0 = mods[0]
+    return (1 <= len(mods) <= 3 and 0 < n_views <= 32
+            and all(m.channel == 256 and m.collapse.out_features == 256 and m.num_grid_layer == m0.num_grid_layer
+                    and m.geometry_key == m0.geometry_key and getattr(m.args, "data", None) == getattr(m0.args, "data", None)
+                    and tuple(m.args.image_size) == tuple(m0.args.image_size) for m in mods))
+
+
 def fused_frame_ok(mods, n_views, mode="fused"):
     """The per-frame-records inference paths (``mode`` "fused": one persistent kernel for everything behind the integral
     images; "window": LDS-window pooling kernel + MFMA collapse kernel per scale) cover these projector modules (one per
     feature scale) for this many cameras."""
-    m0 = mods[0]
     on = FUSED_POOL if mode == "fused" else (WINDOW_POOL and not FUSED_POOL)
-    return (on and COLLAPSE_KERNEL != "library" and 1 <= len(mods) <= 3 and 0 < n_views <= 32
-            and all(m.channel == 256 and m.num_grid_layer == 1 and m.collapse.out_features == 256 for m in mods)
-            and all(m.geometry_key == m0.geometry_key and getattr(m.args, "data", None) == getattr(m0.args, "data", None)
-                    and tuple(m.args.image_size) == tuple(m0.args.image_size) for m in mods))
+    return bool(on and COLLAPSE_KERNEL != "library" and _one_frame_module_set(mods, n_views) and mods[0].num_grid_layer == 1)
 
 
 def fused_frame(mods, features, calibs, grid, crange=(-1, 0.95), out=None, accumulate=False, reserved_cus=0, integrals=None):
@@ -240,14 +246,9 @@ def pipe_frame_ok(mods, n_views, tensors=()):
     """The pipelined per-frame inference path covers these projector modules (one per feature scale; any layer count, the
     same for all) for this many cameras, and no gradient is wanted (of the weights, biases or ``tensors``: pass the features and
     the geometry -- calibs, grid -- of the call)."""
-    m0 = mods[0]
-    if not (PIPE and COLLAPSE_KERNEL != "library" and 1 <= len(mods) <= 3 and 0 < n_views <= 32):
+    if not (PIPE and COLLAPSE_KERNEL != "library" and _one_frame_module_set(mods, n_views)):
         return False
-    if m0.num_grid_layer == 1 and not PIPE_SINGLE_LAYER:
-        return False
-    if not all(m.channel == 256 and m.collapse.out_features == 256 and m.num_grid_layer == m0.num_grid_layer
-               and m.geometry_key == m0.geometry_key and getattr(m.args, "data", None) == getattr(m0.args, "data", None)
-               and tuple(m.args.image_size) == tuple(m0.args.image_size) for m in mods):
+    if mods[0].num_grid_layer == 1 and not PIPE_SINGLE_LAYER:
         return False
     if not torch.is_grad_enabled():
         return True
@@ -338,12 +339,7 @@ def pipe_frame(mods, features, calibs, grid, crange=(-1, 0.95), out=None, accumu
 def pipe_frames_ok(mods, n_views, tensors=()):
     """``pipe_frame_ok`` for a batch of frames of one rig (``pipe_frames``): single-layer grids included -- the batched launch exists
     in the pipelined kernel only.  ``tensors``: the features and the geometry (calibs, grid) of the call -- no gradient may be wanted."""
-    m0 = mods[0]
-    if not (PIPE and COLLAPSE_KERNEL != "library" and 1 <= len(mods) <= 3 and 0 < n_views <= 32):
-        return False
-    if not all(m.channel == 256 and m.collapse.out_features == 256 and m.num_grid_layer == m0.num_grid_layer
-               and m.geometry_key == m0.geometry_key and getattr(m.args, "data", None) == getattr(m0.args, "data", None)
-               and tuple(m.args.image_size) == tuple(m0.args.image_size) for m in mods):
+    if not (PIPE and COLLAPSE_KERNEL != "library" and _one_frame_module_set(mods, n_views)):
         return False
     if not torch.is_grad_enabled():
         return True
@@ -521,11 +517,7 @@ FUSED_TRAIN = os.environ.get("VFA_AMD_FUSED_TRAIN", "1") == "1"
 
 def _frame_kernels_cover(mods, n_views):
     """Module set / camera count the fused per-frame kernels cover (gradients or not)."""
-    m0 = mods[0]
-    return (COLLAPSE_KERNEL != "library" and 1 <= len(mods) <= 3 and 0 < n_views <= 32
-            and all(m.channel == 256 and m.collapse.out_features == 256 and m.num_grid_layer == m0.num_grid_layer
-                    and m.geometry_key == m0.geometry_key and getattr(m.args, "data", None) == getattr(m0.args, "data", None)
-                    and tuple(m.args.image_size) == tuple(m0.args.image_size) for m in mods))
+    return COLLAPSE_KERNEL != "library" and _one_frame_module_set(mods, n_views)
 
 
 class _FusedFrameTrain(torch.autograd.Function):
