@@ -1,4 +1,4 @@
-"""``vfa.evaluation``: ``pyeval.evaluateAPAOS`` comes from the MI355X build; the rest of the reference's ``vfa/evaluation``
+"""``vfa.evaluation``: ``pyeval.evaluateAPAOS`` and ``pyeval.evaluateDetection`` come from the MI355X build; the rest of the reference's ``vfa/evaluation``
 directory (evaluate.py, the MATLAB kit) is appended to the package path when it is present."""
 import os
 

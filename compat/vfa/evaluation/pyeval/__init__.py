@@ -1,5 +1,5 @@
-"""``vfa.evaluation.pyeval``: `evaluateAPAOS` is the alias module next to this file; every other module of the reference's
-``vfa/evaluation/pyeval`` directory (IoU.py, CLEAR_MOD_HUN.py, evaluateDetection.py, cuda_op/) still resolves to the checkout."""
+"""``vfa.evaluation.pyeval``: `evaluateAPAOS` and `evaluateDetection` are the alias modules next to this file; every other module of
+the reference's ``vfa/evaluation/pyeval`` directory (IoU.py, CLEAR_MOD_HUN.py, cuda_op/) still resolves to the checkout."""
 import os
 
 from ... import _reference_dirs

@@ -23,6 +23,8 @@
  *     the reference's (79-87 % of them identical: VFA_FLAG_DUMP_VOX, tests/test_fused_frame.py), and
  *     their output is compared with the reference within the post-GEMM tolerance (rtol 1e-4, atol 1e-5 max|ref|);
  *   - `n_views` batches cameras that share feature-map and grid shapes (one scale of one frame).
+ * The consumers at the end of the header (BEV decode, the AP/AOS metric, the CLEAR-MOD metric) follow the same conventions; the
+ * CLEAR-MOD entry point alone is float64, like the reference's numpy (vfa_clear_mod_frames_f64).
  *
  * Layouts
  *   feature   (n_views, C, Hf, Wf)          NCHW, as the reference's lateral maps
@@ -657,6 +659,46 @@ int vfa_bev_nms_batch_f32(const float *heatmap, float *conf, int B, int L, int W
 int vfa_iou3d_f32(const float *box1, const float *box2, float *iou3d, float *iou_bev, long long count, void *stream);
 int vfa_iou3d_frames_f32(const float *det, const int *det_begin, const float *gt, const int *gt_begin, int n_frames, int n_det, int n_gt,
                          const long long *pair_begin, long long n_pairs, float *iou, int *best_idx, float *best_iou, void *stream);
+
+/* ---- the CLEAR-MOD metric (MODA / MODP): distances and the Hungarian assignment of every frame --------------------------------
+ *
+ * vfa_clear_mod_frames_f64: the match tables of a whole 2D evaluation set in one launch, ONE WAVE PER FRAME (grid = n_frames; the
+ * workgroups share nothing: no atomics, no workspace, the same bits on every run).
+ *                                                            replaces the frame loop of vfa/evaluation/pyeval/CLEAR_MOD_HUN.py:44-93
+ *   det_xy (n_det, 2), gt_xy (n_gt, 2) float64 ground positions, rows sorted by frame; det_begin, gt_begin (n_frames + 1) int32 CSR
+ *   offsets of the frames' rows, as vfa_iou3d_frames_f32 takes them; td the distance threshold (the reference's 30).
+ *   Per frame, in float64 like the reference's numpy:
+ *   - d(o, e) = sqrt((gx - ex) * (gx - ex) + (gy - ey) * (gy - ey)), no contraction: the bits of numpy's sqrt (:6-7, :63);
+ *   - cost = d > td ? 1e6 : d (:69); a non-finite distance costs 1e6 too (a deviation: the reference lets scipy raise);
+ *   - the minimum-cost assignment of min(G_f, P_f) pairs, what scipy.optimize.linear_sum_assignment solves (:72): shortest
+ *     augmenting paths with duals (Jonker-Volgenant), the smaller side as rows, the lanes spread over the columns, the lowest
+ *     column index on a tie; duals, slacks, predecessors and both match arrays in LDS, the cost matrix too when rows * cols <=
+ *     2048, otherwise costs are computed again from the frame's coordinates in LDS.  Every loop is bounded (at most rows
+ *     augmentations of at most cols + 1 steps) whatever the costs are;
+ *   - a pair is a match when its assigned cost is < td (:73).  Kept quirk: a pair at exactly td keeps the cost td, competes in
+ *     the assignment and is NOT a match.  Among assignments of equal cost the choice is unspecified, here as in scipy.
+ *   Out:
+ *   - gt_match (n_gt) int32: frame-local index of the matched detection, or -1; gt_dist (n_gt) float64: its distance, +inf where
+ *     unmatched (the reference's `distances`, :42, :91);
+ *   - frame_counts (n_frames, 4) int64: G_f, P_f, c = number of matches, number of pairs assigned at 1e6 (fp = P_f - c and
+ *     m = G_f - c are the reference's :92-93); frame_cost (n_frames) float64: sum of the assigned costs below 1e6, added in
+ *     ground-truth order; frame_status (n_frames) int32, 0 or one of VFA_CLEAR_MOD_*;
+ *   - dist (n_pairs) float64 or NULL: the frames' distance matrices before the threshold, ground-truth-major like the reference's
+ *     dist[o, e]; pair_begin (n_frames + 1) int64 their offsets, n_pairs = sum G_f * P_f (a matrix that would leave [0, n_pairs) is
+ *     not written).
+ *   Limits: frames up to max(P_f, G_f) <= VFA_CLEAR_MOD_MAX_SIDE.  A larger frame gets status VFA_CLEAR_MOD_TOO_LARGE, -1 / +inf in
+ *   its rows of gt_match / gt_dist, and nothing else of it is written.  Offsets that are not non-decreasing within [0, n_det] /
+ *   [0, n_gt] are not followed: status VFA_CLEAR_MOD_BAD_OFFSETS and nothing else written.  VFA_CLEAR_MOD_SOLVER_FLAG: a loop of
+ *   the solver met its bound (not reachable with finite td; the tables of that frame are not to be used).  Rows outside
+ *   [gt_begin[0], gt_begin[n_frames]) are not touched.
+ *   Errors: negative counts or a NULL required pointer (pair_begin with dist): VFA_ERR_BAD_ARGUMENT; n_frames == 0 returns 0. */
+#define VFA_CLEAR_MOD_MAX_SIDE 512
+#define VFA_CLEAR_MOD_TOO_LARGE 1
+#define VFA_CLEAR_MOD_BAD_OFFSETS 2
+#define VFA_CLEAR_MOD_SOLVER_FLAG 3
+int vfa_clear_mod_frames_f64(const double *det_xy, const int *det_begin, const double *gt_xy, const int *gt_begin, int n_frames, int n_det,
+                             int n_gt, double td, const long long *pair_begin, long long n_pairs, double *dist, int *gt_match,
+                             double *gt_dist, long long *frame_counts, double *frame_cost, int *frame_status, void *stream);
 
 #ifdef __cplusplus
 }

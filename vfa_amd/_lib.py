@@ -27,6 +27,7 @@ def collapse_flags(terms=0, reserved_cus=0):
 
 
 _c_int, _c_float, _c_size_t, _vp, _c_longlong = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_longlong
+_c_double = ctypes.c_double
 
 # name -> argtypes; must list every symbol include/vfa_hip.h declares (tests/test_abi.py checks it)
 SIGNATURES = {
@@ -120,6 +121,7 @@ SIGNATURES = {
     "vfa_bev_nms_batch_f32": [_vp, _vp, _c_int, _c_int, _c_int, _vp],
     "vfa_iou3d_f32": [_vp, _vp, _vp, _vp, _c_longlong, _vp],
     "vfa_iou3d_frames_f32": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _c_longlong, _vp, _vp, _vp, _vp],
+    "vfa_clear_mod_frames_f64": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_double, _vp, _c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 _lib = None

@@ -11,7 +11,12 @@
   evaluation set per launch, the best ground truth of every detection without a host round trip per pair.
 * ``ap_aos_from_matches`` / ``ap_aos`` / ``evaluate_ap_aos``  -- the AP / AOS metric built on them (``evaluateAPAOS.py``);
   ``evaluate_ap_aos`` has the signature and the 9-tuple of the reference's ``evaluateDetectionAPAOS``.
+* ``match_frames_hungarian`` / ``clear_mod`` / ``evaluate_detection``  -- the MODA / MODP metric of the 2D sets (``CLEAR_MOD_HUN.py``,
+  ``evaluateDetection.py``): distances and the Hungarian assignment of every frame of an evaluation set in one launch, one wave per
+  frame (``vfa_clear_mod_frames_f64``); ``evaluate_detection`` has the signature and the 4-tuple of ``evaluateDetection_py``.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -255,6 +260,148 @@ def evaluate_ap_aos(res_fpath, gt_fpath):
     for ap, aos in ap_aos(gt_raw, det_raw, (0.75, 0.5, 0.25)):
         out += [ap * 100, aos * 100, aos / ap if ap else float("nan")]
     return tuple(out)
+
+
+HungarianTables = collections.namedtuple("HungarianTables", "gt_match gt_dist frame_counts frame_cost frame_status dist pair_begin")
+CLEAR_MOD_MAX_SIDE = 512  # VFA_CLEAR_MOD_MAX_SIDE (include/vfa_hip.h)
+
+
+def _xy_rows(t, name):
+    if t.dim() != 2 or t.shape[1] != 2:
+        raise ValueError(f"{name} must be (n, 2) ground positions x y, got {tuple(t.shape)}")
+    return t.to(torch.float64).contiguous()
+
+
+def match_frames_hungarian(det_xy, det_frame, gt_xy, gt_frame, n_frames=None, td=30.0, with_matrix=False):
+    """The match tables of the CLEAR-MOD metric for a whole evaluation set in one launch (``vfa_clear_mod_frames_f64``): per frame
+    the distances, the reference's cost ``d > td -> 1e6`` and the minimum-cost assignment ``scipy.optimize.linear_sum_assignment``
+    solves (``CLEAR_MOD_HUN.py:58-73``), one wave per frame.
+
+    ``det_xy (P, 2)``, ``gt_xy (G, 2)`` ground positions (converted to float64, the reference's precision); ``det_frame (P)``,
+    ``gt_frame (G)`` integer frame counters ``0 .. n_frames - 1``, each NON-DECREASING, with the conventions of ``match_frames``:
+    ``n_frames`` given, nothing here waits for the device and the counters are not checked; ``None``, it is taken from the largest
+    counter, which costs one host synchronisation that also checks the order.
+    Returns ``HungarianTables``: ``gt_match (G)`` int32 -- index of the matched detection WITHIN ITS FRAME, -1 when unmatched;
+    ``gt_dist (G)`` float64 -- its distance, +inf when unmatched (the reference's ``distances``); ``frame_counts (n_frames, 4)``
+    int64 -- ground truths, detections, matches ``c``, pairs assigned at 1e6; ``frame_cost (n_frames)`` float64 -- sum of the
+    assigned costs below 1e6; ``frame_status (n_frames)`` int32 -- 0, or 1 for a frame with more than ``CLEAR_MOD_MAX_SIDE``
+    ground truths or detections (its rows are -1 / +inf, its counts 0).  A pair is a match when its assigned cost is ``< td``; a
+    pair at exactly ``td`` competes in the assignment and is not a match (the reference's).  ``with_matrix=True`` also fills
+    ``dist`` and ``pair_begin``: frame ``f``'s ``(G_f, P_f)`` matrix of distances is ``dist[pair_begin[f]:pair_begin[f + 1]]``,
+    ground-truth-major like the reference's ``dist[o, e]`` (one more synchronisation, for its size)."""
+    _lib.require_device(det_xy, det_frame, gt_xy, gt_frame)
+    det_xy, gt_xy = _xy_rows(det_xy, "det_xy"), _xy_rows(gt_xy, "gt_xy")
+    det_frame, gt_frame = det_frame.to(torch.int64).contiguous(), gt_frame.to(torch.int64).contiguous()
+    if det_frame.shape != (det_xy.shape[0],) or gt_frame.shape != (gt_xy.shape[0],):
+        raise ValueError("one frame counter per position is needed")
+    dev = det_xy.device
+    if n_frames is None:
+        both = torch.cat([det_frame, gt_frame])
+        if both.numel() == 0:
+            n_frames = 0
+        else:
+            ordered = torch.stack([(det_frame[1:] >= det_frame[:-1]).all(), (gt_frame[1:] >= gt_frame[:-1]).all(), both.min() >= 0])
+            hi, ok = int(both.max()), bool(ordered.all())
+            if not ok:
+                raise ValueError("match_frames_hungarian: frame counters must be non-negative and sorted (non-decreasing)")
+            n_frames = hi + 1
+    edges = torch.arange(n_frames + 1, dtype=torch.int64, device=dev)
+    det_begin64, gt_begin64 = torch.searchsorted(det_frame, edges), torch.searchsorted(gt_frame, edges)
+    det_begin, gt_begin = det_begin64.to(torch.int32), gt_begin64.to(torch.int32)
+    G = gt_xy.shape[0]
+    gt_match = torch.full((G,), -1, dtype=torch.int32, device=dev)
+    gt_dist = torch.full((G,), float("inf"), dtype=torch.float64, device=dev)
+    frame_counts = torch.zeros((n_frames, 4), dtype=torch.int64, device=dev)
+    frame_cost = torch.zeros(n_frames, dtype=torch.float64, device=dev)
+    frame_status = torch.zeros(n_frames, dtype=torch.int32, device=dev)
+    dist = pair_begin = None
+    n_pairs = 0
+    if with_matrix:
+        pair_begin = torch.zeros(n_frames + 1, dtype=torch.int64, device=dev)
+        pair_begin[1:] = torch.cumsum((det_begin64[1:] - det_begin64[:-1]) * (gt_begin64[1:] - gt_begin64[:-1]), 0)
+        n_pairs = int(pair_begin[-1])
+        dist = torch.full((n_pairs,), float("nan"), dtype=torch.float64, device=dev)
+    _lib.call("vfa_clear_mod_frames_f64", _lib.ptr(det_xy), _lib.ptr(det_begin), _lib.ptr(gt_xy), _lib.ptr(gt_begin), n_frames,
+              det_xy.shape[0], G, float(td), _lib.ptr(pair_begin), n_pairs, _lib.ptr(dist), _lib.ptr(gt_match), _lib.ptr(gt_dist),
+              _lib.ptr(frame_counts), _lib.ptr(frame_cost), _lib.ptr(frame_status), _lib.current_stream_handle())
+    return HungarianTables(gt_match, gt_dist, frame_counts, frame_cost, frame_status, dist, pair_begin)
+
+
+def clear_mod_totals(gt, det, td=30.0, device="cuda"):
+    """The sums behind ``clear_mod`` -> ``(c, fp, m, g, distances)``: matches, false positives, misses and ground truths summed
+    over the frames the reference walks, and the matched distances in (frame, ground truth) order.  Raises what ``clear_mod`` raises;
+    ``det`` must not be empty."""
+    gt, det = _table(gt, 3, "gt"), _table(det, 3, "det")
+    if det.shape[0] == 0:
+        raise ValueError("detection is empty")
+    if not (np.isfinite(gt).all() and np.isfinite(det).all()):
+        raise ValueError("clear_mod: frame numbers and coordinates must be finite")
+    frames = np.unique(det[:, 0])
+    det_ctr = np.searchsorted(frames, det[:, 0])
+    det = det[np.argsort(det_ctr, kind="stable")]
+    det_ctr = np.sort(det_ctr)
+    gt = gt[np.isin(gt[:, 0], frames)]
+    if gt.shape[0] == 0:
+        raise ValueError("no ground truth in the frames that have detections")
+    gt_ctr = np.searchsorted(frames, gt[:, 0])
+    gt = gt[np.argsort(gt_ctr, kind="stable")]
+    gt_ctr = np.sort(gt_ctr)
+    n_frames = int(gt_ctr.max()) + 1
+    det, det_ctr = det[det_ctr < n_frames], det_ctr[det_ctr < n_frames]
+    sizes = np.maximum(np.bincount(det_ctr, minlength=n_frames), np.bincount(gt_ctr, minlength=n_frames))
+    if sizes.max() > CLEAR_MOD_MAX_SIDE:
+        worst = int(np.argmax(sizes))
+        raise ValueError(f"clear_mod: frame {frames[worst]:g} has {sizes[worst]} ground truths or detections, more than the "
+                         f"{CLEAR_MOD_MAX_SIDE} one wave solves")
+    dev = torch.device(device)
+    t = match_frames_hungarian(torch.from_numpy(det[:, 1:3]).to(dev), torch.from_numpy(det_ctr).to(dev),
+                               torch.from_numpy(gt[:, 1:3]).to(dev), torch.from_numpy(gt_ctr).to(dev), n_frames=n_frames, td=td)
+    counts, status, distances = t.frame_counts.cpu().numpy(), t.frame_status.cpu().numpy(), t.gt_dist.cpu().numpy()
+    if status.any():
+        raise _lib.VFAHipError(f"vfa_clear_mod_frames_f64: status {status.max()} in frame {frames[int(np.argmax(status))]:g}")
+    g, n_det, c = (int(v) for v in counts[:, :3].sum(axis=0))
+    return c, n_det - c, g - c, g, distances
+
+
+def clear_mod(gt, det, td=30.0, device="cuda"):
+    """The reference's ``CLEAR_MOD_HUN`` behind ``evaluateDetection_py`` -> ``(recall, precision, MODA, MODP)`` in per cent; the
+    distances and the Hungarian assignment of every frame in one launch (``match_frames_hungarian``).
+
+    ``gt`` and ``det``: arrays in the reference's text layout, rows ``frame x y``.  The bookkeeping is the reference's, quirks kept:
+    * the frames are those that HAVE detections; ground truth of other frames does not count (``evaluateDetection.py:30, 41-42``);
+    * the frame counters run to the last frame that has ground truth (``CLEAR_MOD_HUN.py:29``): detections of later frames are
+      dropped, frames in between that have detections and no ground truth count as false positives;
+    * per frame ``fp = n_det - c`` and ``m = g - c`` (``:92-93``); a pair at exactly ``td`` competes in the assignment and is not a
+      match (``:69, :73``);
+    * MODP is ``sum(1 - d / td)`` over the matched pairs, added in (frame, ground truth) order like the reference's builtin ``sum``,
+      over ``sum(c)``, times 100 (``:94``); MODA ``(1 - (sum(m) + sum(fp)) / sum(g)) * 100``; recall ``sum(c) / sum(g) * 100``;
+      precision ``sum(c) / (sum(fp) + sum(c)) * 100``;
+    * every metric that is not ``> 0`` becomes 0 (``:94-99``), the 0 / 0 of a set without matches included (no numpy warning here).
+    No detections: ``(0, 0, 0, 0)`` (``evaluateDetection.py:37-39``).  ``ValueError``: no ground truth in the frames that have
+    detections (the reference fails there on ``max`` of an empty array), non-finite input, a frame with more than
+    ``CLEAR_MOD_MAX_SIDE`` ground truths or detections (named in the message)."""
+    if _table(det, 3, "det").shape[0] == 0:
+        return 0, 0, 0, 0
+    c, fp, m, g, distances = clear_mod_totals(gt, det, td, device)
+    td = float(td)
+
+    def positive(v):
+        return v if v > 0 else 0
+    modp = sum(1 - distances[distances < td] / td) / c * 100 if c else 0
+    return positive(c / g * 100), positive(c / (fp + c) * 100), positive((1 - (m + fp) / g) * 100), positive(modp)
+
+
+def evaluate_detection(res_fpath, gt_fpath, dataset_name=None):
+    """The reference's ``evaluateDetection_py(res_fpath, gt_fpath, dataset_name)`` (``evaluateDetection.py:6-72``): two text files
+    of rows ``frame x y`` -> ``(recall, precision, MODA, MODP)`` in per cent.  ``dataset_name`` is ignored, as the reference
+    ignores it."""
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)  # (loadtxt's "input contained no data" for an empty result file)
+        gt_raw, det_raw = np.loadtxt(gt_fpath, ndmin=2), np.loadtxt(res_fpath, ndmin=2)
+    if det_raw.shape[0] == 0 or det_raw.size == 0:
+        return 0, 0, 0, 0
+    return clear_mod(gt_raw[:, :3], det_raw[:, :3])
 
 
 class BEVDecoder:
