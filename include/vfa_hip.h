@@ -700,6 +700,43 @@ int vfa_clear_mod_frames_f64(const double *det_xy, const int *det_begin, const d
                              int n_gt, double td, const long long *pair_begin, long long n_pairs, double *dist, int *gt_match,
                              double *gt_dist, long long *frame_counts, double *frame_cost, int *frame_status, void *stream);
 
+/* ---- the BEV decode: heads of a batch of frames -> detections, outputs of a fixed shape ----------------------------------------
+ *
+ * vfa_bev_decode_f32: peaks, top-k, box arithmetic and the rotation arg-max of B frames in one stream-ordered call: two launches
+ * (the kernel of vfa_bev_nms_batch_f32 into the workspace, then one workgroup per frame), no allocation, no host round trip, no
+ * atomics on memory: the same bits on every run.  Nothing crosses from one frame into another.
+ *                                                            replaces vfa/data/encoder.py:234-305 (decode3d / decode2d)
+ *   heatmap (B, 1, L, W) logits, contiguous.  loc_offset (B, L, W, 2), dim_offset (B, L, W, 3), rotation (B, L, W, n_rot) logits,
+ *   each read through four ELEMENT strides {frame, cell row, cell column, channel} given as a HOST array, so a permute(0, 2, 3, 1)
+ *   view of NCHW storage and a contiguous NHWC tensor are taken alike and no head is ever copied.  dim_offset == rotation == NULL:
+ *   2D (dim_stride, rot_stride, dimension_mean, dimension, rotation_out are then ignored).  dimension_mean: 3 floats on the HOST.
+ *   Per frame, k = min(topk, L * W):
+ *   - conf[l, w] is what vfa_bev_nms_batch_f32 writes, bit for bit; a CANDIDATE is a cell with conf > cls_thresh;
+ *   - the k candidates that come first by confidence descending, equal confidences by ascending flat cell index l * W + w, in that
+ *     order: exact for any number of candidates (a constant map gives cells 0 .. k - 1).  For cls_thresh >= 0 this is the
+ *     reference's top-k followed by its threshold, with the order among equal confidences (which torch.topk leaves open) fixed;
+ *   - per selected cell, fp32, one operation per reference operation, s(x) = 1.0f / (1.0f + expf(-x)):
+ *       cy = (l + s(loc[0])) / grid0 * world0,  cx = (w + s(loc[1])) / grid1 * world1,
+ *       location = (cx, cy, 0), or (cy, cx, 0) with yx_first != 0 (the reference's 2D Wildtrack);
+ *       dimension[j] = expf(dim[j]) * dimension_mean[j];
+ *       rotation = (float)argmax * (float)(pi / 180), the arg-max over s(rotation[0 .. n_rot)), the FIRST index that attains the
+ *       maximum (saturated logits tie at 1.0f like the reference's); a NaN never wins, all NaN gives index 0.
+ *   Out, all written by the call: count (B) int32 = number of detections of the frame; conf (B, k); location (B, k, 3); cell (B, k)
+ *   int32 = l * W + w; in 3D dimension (B, k, 3) and rotation_out (B, k).  Rows from count[b] on are zeros, their cell -1.
+ *   Every loop is bounded by a count known before it starts (digit passes, cells, k, n_rot); NaN or +-Inf logits give no candidate
+ *   or an unspecified one, never a read or write outside the buffers.
+ *   workspace: vfa_bev_decode_workspace_bytes(B, L, W, topk) bytes (the confidence maps), 4-byte aligned, the caller's.
+ *   Limits and errors: a negative size, topk < 1, a NULL required pointer, a short workspace, cls_thresh < 0 or NaN:
+ *   VFA_ERR_BAD_ARGUMENT; B == 0 or L * W == 0 returns 0 and writes nothing; B > 65535, topk > VFA_BEV_DECODE_MAX_TOPK or
+ *   L * W >= 2^31: VFA_ERR_UNSUPPORTED. */
+#define VFA_BEV_DECODE_MAX_TOPK 1024
+size_t vfa_bev_decode_workspace_bytes(int B, int L, int W, int topk);
+int vfa_bev_decode_f32(const float *heatmap, const float *loc_offset, const long long *loc_stride, const float *dim_offset,
+                       const long long *dim_stride, const float *rotation, const long long *rot_stride, int B, int L, int W, int n_rot,
+                       int topk, float cls_thresh, float grid0, float grid1, float world0, float world1, const float *dimension_mean,
+                       int yx_first, void *workspace, size_t workspace_bytes, int *count, float *conf, float *location, int *cell,
+                       float *dimension, float *rotation_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

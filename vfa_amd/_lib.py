@@ -122,6 +122,9 @@ SIGNATURES = {
     "vfa_iou3d_f32": [_vp, _vp, _vp, _vp, _c_longlong, _vp],
     "vfa_iou3d_frames_f32": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _c_longlong, _vp, _vp, _vp, _vp],
     "vfa_clear_mod_frames_f64": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_double, _vp, _c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "vfa_bev_decode_workspace_bytes": [_c_int, _c_int, _c_int, _c_int],
+    "vfa_bev_decode_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float,
+                           _c_float, _c_float, _vp, _c_int, _vp, _c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 _lib = None

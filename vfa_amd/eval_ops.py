@@ -5,7 +5,8 @@
   ``vfa_sort_vertices_f32``.  ``evaluateAPAOS.py:79-83`` hard-codes ``device('cuda')``, which IS the MI355X under PyTorch-ROCm.
 * ``BEVDecoder``  -- ``ObjectEncoder.nms / decode3d / decode2d`` (``vfa/data/encoder.py:230-305``) with the dataset constants
   passed explicitly: sigmoid + 5x5 max-pool NMS in one HIP kernel (``vfa_bev_nms_f32``), then top-k and the gathers (torch ops on
-  the device: a few hundred numbers).
+  the device: a few hundred numbers).  ``BEVDecoder.decode_fused`` does the whole decode of a batch of frames in one call
+  (``vfa_bev_decode_f32``) with outputs of a fixed shape and no host wait; ``split`` and ``flat_detections`` hand them on.
 * ``iou3d`` / ``iou_bev`` / ``iou3d_matrix`` / ``match_frames``  -- the reference's rotated-box ``IoU3D`` (``vfa/evaluation/pyeval/
   IoU.py:206-225``) with one GPU lane per box pair (``vfa_iou3d_f32``, ``vfa_iou3d_frames_f32``): any batch shape, a whole
   evaluation set per launch, the best ground truth of every detection without a host round trip per pair.
@@ -16,6 +17,7 @@
   frame (``vfa_clear_mod_frames_f64``); ``evaluate_detection`` has the signature and the 4-tuple of ``evaluateDetection_py``.
 """
 import collections
+import ctypes
 
 import numpy as np
 import torch
@@ -404,6 +406,33 @@ def evaluate_detection(res_fpath, gt_fpath, dataset_name=None):
     return clear_mod(gt_raw[:, :3], det_raw[:, :3])
 
 
+DECODE_MAX_TOPK = 1024  # VFA_BEV_DECODE_MAX_TOPK (include/vfa_hip.h)
+
+
+def flat_detections(fused):
+    """``BEVDecoder.decode_fused``'s result -> ``(rows, frame_index, n_frames)`` for ``match_frames`` /
+    ``match_frames_hungarian`` with ``n_frames`` given: a batch goes from heads to match tables without the host seeing a count.
+
+    The ``B * k`` rows are compacted on the device, shapes fixed: a stable sort by frame counter brings the detections to the front
+    in (frame, rank) order; the unused rows follow with the counter ``n_frames = B``, which puts them behind the last frame's end
+    in the offset tables both functions build, so neither reads them (``match_frames`` returns -1 / -1 for them).  ``rows``:
+    ``conf (B k)``, ``location (B k, 3)``, ``cell (B k)``, ``xy (B k, 2)`` -- the ground positions ``match_frames_hungarian``
+    takes -- and in 3D ``dimension``, ``rotation`` and ``box (B k, 7)`` = ``x y z l w h alpha``, the rows ``match_frames`` takes
+    (the dimension reversed, as the reference writes its result file, evaluate.py:95-102)."""
+    count, conf = fused["count"], fused["conf"]
+    B, k = conf.shape
+    rank = torch.arange(k, device=conf.device)
+    frame = torch.arange(B, device=conf.device)[:, None].expand(B, k)
+    frame_index = torch.where(rank[None, :] < count[:, None], frame, torch.full_like(frame, B)).reshape(-1)
+    frame_index, order = torch.sort(frame_index, stable=True)
+    rows = {name: fused[name].reshape(B * k, *fused[name].shape[2:])[order] for name in ("conf", "location", "cell", "dimension", "rotation")
+            if name in fused}
+    rows["xy"] = rows["location"][:, :2]
+    if "dimension" in rows:
+        rows["box"] = torch.cat([rows["location"], rows["dimension"].flip(-1), rows["rotation"][:, None]], dim=1)
+    return rows, frame_index, B
+
+
 class BEVDecoder:
     """``ObjectEncoder``'s decode half (encoder.py:230-305).  ``base`` is the dataset class name, ``world_size`` / ``cube_LWH``
     as in the dataset configs, ``dimension_mean`` = ``classAverage.get_mean(...)`` (3D only)."""
@@ -472,3 +501,73 @@ class BEVDecoder:
             finally:
                 self._conf = None
         return out
+
+    def decode_fused(self, pred, cls_thresh):
+        """A batch of B >= 1 frames (every head ``(B, ...)``) -> detections in tensors of a FIXED shape, in one library call
+        (``vfa_bev_decode_f32``): nothing here waits for the device or reads a value back, so the call can be captured by
+        ``torch.cuda.graph`` and its result handed on (``flat_detections``) without the host seeing a count.
+
+        ``pred``: ``heatmap (B, 1, L, W)``, ``loc_offset (B, L, W, 2)`` and, for the 3D bases, ``dim_offset (B, L, W, 3)`` and
+        ``rotation (B, L, W, R)``, float32; the three heads are read through their strides, so ``VFANet``'s ``permute(0, 2, 3, 1)``
+        views and contiguous tensors are taken alike and never copied.  Returns, with ``k = min(topk, L * W)``: ``count (B)`` int32;
+        ``conf (B, k)``; ``location (B, k, 3)``; ``cell (B, k)`` int32, the flat index ``l * W + w``; in 3D ``dimension (B, k, 3)``
+        and ``rotation (B, k)``.  Frame ``b``'s detections are rows ``0 .. count[b] - 1``: those ``batch_decode`` gives for it (cells
+        with ``conf > cls_thresh`` among the top k), by confidence descending, EQUAL confidences by ascending cell (``torch.topk``
+        leaves that order open); the rows behind them are zeros with ``cell`` -1.  ``ValueError``: ``cls_thresh < 0`` (the
+        equivalence with top-k-then-threshold needs it), ``topk`` outside 1 .. 1024, a 3D base without ``dimension_mean``."""
+        three_d = self.base in ("MultiviewC", "MVM3D")
+        if not float(cls_thresh) >= 0:
+            raise ValueError(f"decode_fused: cls_thresh must be >= 0, got {cls_thresh}")
+        if not 1 <= int(self.topk) <= DECODE_MAX_TOPK:
+            raise ValueError(f"decode_fused: topk must be in 1 .. {DECODE_MAX_TOPK}, got {self.topk}")
+        if three_d and self.dimension_mean is None:
+            raise ValueError(f"decode_fused: base {self.base} decodes 3D boxes and needs dimension_mean")
+        names = ("heatmap", "loc_offset") + (("dim_offset", "rotation") if three_d else ())
+        _lib.require_device(*(pred[n] for n in names))
+        heat = pred["heatmap"].to(torch.float32).contiguous()
+        if heat.dim() != 4 or heat.shape[1] != 1:
+            raise ValueError(f"decode_fused: heatmap must be (B, 1, L, W), got {tuple(heat.shape)}")
+        B, _, L, W = heat.shape
+        dev = heat.device
+
+        def head(name, channels):
+            t = pred[name]
+            if t.dtype != torch.float32 or t.dim() != 4 or tuple(t.shape[:3]) != (B, L, W) or (channels and t.shape[3] != channels):
+                raise ValueError(f"decode_fused: {name} must be float32 (B, L, W, {channels or 'R'}) = ({B}, {L}, {W}, ...), got "
+                                 f"{t.dtype} {tuple(t.shape)}")
+            return t, (ctypes.c_longlong * 4)(*t.stride())
+        loc, loc_stride = head("loc_offset", 2)
+        dim = rot = dim_stride = rot_stride = mean = None
+        n_rot = 0
+        if three_d:
+            dim, dim_stride = head("dim_offset", 3)
+            rot, rot_stride = head("rotation", 0)
+            n_rot = rot.shape[3]
+            if n_rot < 1:
+                raise ValueError("decode_fused: rotation needs at least one channel")
+            mean = (ctypes.c_float * 3)(*[float(m) for m in self.dimension_mean])
+        k = min(int(self.topk), L * W)
+        empty = B * L * W == 0
+        out = {"count": torch.zeros(B, dtype=torch.int32, device=dev) if empty else torch.empty(B, dtype=torch.int32, device=dev),
+               "conf": torch.empty((B, k), dtype=torch.float32, device=dev),
+               "location": torch.empty((B, k, 3), dtype=torch.float32, device=dev),
+               "cell": torch.empty((B, k), dtype=torch.int32, device=dev)}
+        if three_d:
+            out["dimension"] = torch.empty((B, k, 3), dtype=torch.float32, device=dev)
+            out["rotation"] = torch.empty((B, k), dtype=torch.float32, device=dev)
+        ws_bytes = _lib.lib().vfa_bev_decode_workspace_bytes(B, L, W, int(self.topk))
+        ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
+        _lib.call("vfa_bev_decode_f32", _lib.ptr(heat), _lib.ptr(loc), loc_stride, _lib.ptr(dim), dim_stride, _lib.ptr(rot), rot_stride,
+                  B, L, W, n_rot, int(self.topk), float(cls_thresh), float(self.grid_size[0]), float(self.grid_size[1]),
+                  float(self.world_size[0]), float(self.world_size[1]), mean, int(self.base == "Wildtrack" and not three_d),
+                  _lib.ptr(ws), ws_bytes, _lib.ptr(out["count"]), _lib.ptr(out["conf"]), _lib.ptr(out["location"]),
+                  _lib.ptr(out["cell"]), _lib.ptr(out.get("dimension")), _lib.ptr(out.get("rotation")), _lib.current_stream_handle())
+        return out
+
+    @staticmethod
+    def split(fused):
+        """``decode_fused``'s result -> a list of B per-frame dicts in ``batch_decode``'s format and dtypes (``conf (n)``,
+        ``location (n, 3)``, in 3D ``dimension (n, 3)`` and ``rotation (n)``).  Reading the counts is the one host wait of the
+        fused path."""
+        keys = [k for k in ("conf", "location", "dimension", "rotation") if k in fused]
+        return [{k: fused[k][b, :n] for k in keys} for b, n in enumerate(fused["count"].tolist())]
