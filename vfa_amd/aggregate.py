@@ -61,6 +61,30 @@ class _ScaleViewSum(torch.autograd.Function):
         return (*outs, *bias_grads)
 
 
+def scale_autograd_frame(mods, lats, calibs, grid, crange, reserved=0):
+    """The "scale_autograd" route of ``vfa_op.run_frame``: per scale the batched projection and the collapse product (differentiable:
+    ``_BoxPool``, ``_CollapseGemm``), then one kernel for the biases, ReLUs, scale sum and view sum -> (L*W, C_out)."""
+    work = tuple(zip(mods, lats))
+    if N_STREAMS == 1 or not grid.is_cuda:
+        lins = [m.project_views(lat, calibs, grid, crange, reserved_cus=reserved) for m, lat in work]
+    else:
+        main = _lib.current_stream(grid.device)
+        side = _streams(grid.device)
+        lins = []
+        for i, (m, lat) in enumerate(work):
+            st = main if i % N_STREAMS == 0 else side[i % N_STREAMS - 1]
+            if st is not main:
+                st.wait_stream(main)  # the inputs (and last step's consumers of recycled memory) are ready
+            with torch.cuda.stream(st):
+                lins.append(m.project_views(lat, calibs, grid, crange, reserved_cus=reserved))
+            if st is not main:
+                lins[-1].record_stream(main)
+        for st in side:
+            main.wait_stream(st)
+    lin8, lin16, lin32 = lins
+    return _ScaleViewSum.apply(lin8, lin16, lin32, *(m.collapse.bias for m in mods))
+
+
 class _ScaleViewMax(torch.autograd.Function):
     """ortho (M,N) = max over views of the scale sum; the winner per element (uint8 (M,N)) is the second, non-differentiable output."""
 
@@ -307,10 +331,11 @@ def _aggregate_frames(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, cran
         raise ValueError(f"aggregate_views(frames={B}): every scale needs {B} x {n} maps, frame-major")
     if B == 0:
         return torch.zeros((0, c_out, length, width), dtype=torch.float32, device=grid.device)
+    # (integral images are not asked whether they want a gradient here: the one launch takes them as they are)
     if (view_reduce == "sum" and calibs.dim() == 3 and not distributed and n > 0
-            and vfa_op.pipe_frames_ok(mods3, n, (calibs, grid) + (() if integrals is not None else (lat8, lat16, lat32)))):
-        ortho = vfa_op.pipe_frames(mods3, None if integrals is not None else [lat8, lat16, lat32], calibs, grid, B, crange,
-                                   integrals=integrals)
+            and vfa_op.frame_route(mods3, n, () if integrals is not None else maps, (calibs, grid), from_integrals=integrals is not None,
+                                   frames=B) == "pipe_batch"):
+        ortho = vfa_op.run_frame("pipe_batch", mods3, maps, calibs, grid, crange, from_integrals=integrals is not None)
         return ortho.view(B, length, width, c_out).permute(0, 3, 1, 2)
     outs = []
     for b in range(B):
@@ -334,12 +359,11 @@ def aggregate_views(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange
     only; ``distributed="reduce_scatter"``: every rank gets its band of BEV rows plus ``halo`` rows of its neighbours (default
     ``HEAD_HALO_ROWS`` = 7: what `fuse` + the dilation-4 heads read; see ``reduce_scatter_ortho`` for what is NOT band-local) and the
     call returns ``(band (1,C,rows,W), (row0, row1), (top, bottom))``.
-    ``integrals``: the three integral-image batches instead of the lateral maps (producer fusion; ``lat*`` may then be None).  With
-    gradients they go through the fused training node (``vfa_op.fused_train_ok``), whose backward hands the channels-last d integral
-    to the producer's node (``VFANet.lateral_integrals``); sum mode only.
+    Which kernels a frame runs through is ``vfa_op.frame_route``'s answer ("Routes of a frame").
+    ``integrals``: the three integral-image batches instead of the lateral maps (producer fusion; ``lat*`` may then be None); per-frame
+    routes and sum mode only.
     ``frames=B``: a batch of B frames -> (B,C,L,W).  lat* (or ``integrals``) hold B*n maps, frame-major; calibs is ONE rig (n,3,4)
-    for every frame, or (B,n,3,4) a rig per frame.  One rig and inference: ONE launch of the pipelined kernel for the whole batch
-    (``vfa_op.pipe_frames``); anything else -- a rig per frame, gradients, distributed reductions -- runs frame by frame and stacks.
+    for every frame, or (B,n,3,4) a rig per frame (then, as with distributed reductions, frame by frame and stacked).
     ``view_reduce``: ``"sum"`` (the reference's ``ortho += vfa_feats``) or ``"max"``: the elementwise maximum of the cameras'
     per-camera maps, each element's gradient going to the lowest camera attaining it.  Max mode runs the per-scale
     path (``project_views`` + ``vfa_scale_view_max_f32``), frame by frame for ``frames=B``, and its ranks reduce with MAX; it takes no
@@ -356,74 +380,20 @@ def aggregate_views(vfa8, vfa16, vfa32, lat8, lat16, lat32, calibs, grid, crange
     # a per-call flag of the MFMA entry points (include/vfa_hip.h: VFA_FLAG_RESERVED_CUS), no library state
     reserved = RESERVED_CUS if (bool(distributed) and dist.is_available() and dist.is_initialized()
                                 and dist.get_world_size(reduce_group) > 1) else 0
-    work = ((vfa8, lat8), (vfa16, lat16), (vfa32, lat32))
     mods3 = [vfa8, vfa16, vfa32]
     argmax = None
     if view_reduce == "max":
         # per scale: batched projection + the collapse product (differentiable: _BoxPool, _CollapseGemm), then ONE kernel for the
         # biases, ReLUs, scale sum and the maximum over cameras (the frame kernels reduce views inside a scale: they cannot)
         if n > 0:
-            lins = [m.project_views(lat, calibs, grid, crange, reserved_cus=reserved) for m, lat in work]
+            lins = [m.project_views(lat, calibs, grid, crange, reserved_cus=reserved) for m, lat in zip(mods3, (lat8, lat16, lat32))]
             ortho, argmax = _ScaleViewMax.apply(*lins, vfa8.collapse.bias, vfa16.collapse.bias, vfa32.collapse.bias)
         else:  # a rank without cameras: zeros, below every camera's map
             ortho = torch.zeros((length * width, vfa8.collapse.out_features), dtype=torch.float32, device=grid.device)
-    elif integrals is not None and n > 0 and vfa_op.fused_train_ok(mods3, n, tuple(integrals), (calibs, grid)):
-        # training on the producer's integral images (``VFANet.lateral_integrals`` / ``vfa_op._LateralIntegrals``): the fused frame node
-        # hands the channels-last d integral back to the producer's node
-        ortho = vfa_op.fused_frame_train(mods3, None, calibs, grid, crange, reserved_cus=reserved, integrals=integrals)
-    elif integrals is not None:
-        assert n > 0 and (vfa_op.pipe_frame_ok(mods3, n) or vfa_op.fused_frame_ok(mods3, n)), \
-            "integral-image inputs need a per-frame path"
-        assert not (torch.is_grad_enabled() and any(i.requires_grad for i in integrals)), \
-            "integral-image inputs with gradients need the fused training node (fused_train_ok)"
-        ortho = torch.empty((length * width, vfa8.collapse.out_features), dtype=torch.float32, device=grid.device)
-        frame = vfa_op.pipe_frame if vfa_op.pipe_frame_ok(mods3, n) else vfa_op.fused_frame
-        frame(mods3, None, calibs, grid, crange, out=ortho, reserved_cus=reserved, integrals=integrals)  # (an ops.IntegralImages keeps its feature statistics)
-    elif n > 0 and vfa_op.fused_train_ok(mods3, n, (lat8, lat16, lat32), (calibs, grid)):
-        # training: the fused kernel in the forward, voxel features and pre-activations recomputed scale by scale in the backward
-        ortho = vfa_op.fused_frame_train(mods3, [lat8, lat16, lat32], calibs, grid, crange, reserved_cus=reserved)
-    elif n > 0 and vfa_op.pipe_frame_ok(mods3, n, (lat8, lat16, lat32, calibs, grid)):
-        # inference, any number of z-layers: geometry once per frame + ONE persistent kernel (pooling waves beside matrix waves)
-        ortho = torch.empty((length * width, vfa8.collapse.out_features), dtype=torch.float32, device=grid.device)
-        vfa_op.pipe_frame(mods3, [lat8, lat16, lat32], calibs, grid, crange, out=ortho, reserved_cus=reserved)
-    elif n > 0 and all(m.mfma_collapse_ok(lat, (calibs, grid)) for m, lat in work):
-        # inference on single-layer grids: per scale, pooling then ONE MFMA kernel that forms collapse + bias + ReLU and
-        # sums the views into the map (sum over views per scale, then over scales: the reference's sums re-associated,
-        # inside the post-GEMM tolerance)
-        ortho = torch.empty((length * width, vfa8.collapse.out_features), dtype=torch.float32, device=grid.device)
-        if vfa_op.fused_frame_ok([vfa8, vfa16, vfa32], n):
-            # geometry once per frame + one persistent kernel for pooling, collapse, ReLU and every sum: vox stays on chip
-            vfa_op.fused_frame([vfa8, vfa16, vfa32], [lat8, lat16, lat32], calibs, grid, crange, out=ortho,
-                               reserved_cus=reserved)
-        elif (vfa_op.fused_frame_ok([vfa8, vfa16, vfa32], n, "window")
-              and n * length * width * 1024 <= vfa_op.VOX_BYTES_LIMIT):
-            # geometry once per frame; per scale: LDS-window pooling kernel (vox in HBM, bit-exact) + MFMA collapse kernel
-            vfa_op.window_frame([vfa8, vfa16, vfa32], [lat8, lat16, lat32], calibs, grid, crange, out=ortho,
-                                reserved_cus=reserved)
-        else:
-            for i, (m, lat) in enumerate(work):
-                m.project_sum(lat, calibs, grid, crange, out=ortho, accumulate=i > 0, reserved_cus=reserved)
-    elif n > 0:
-        if N_STREAMS == 1 or not grid.is_cuda:
-            lins = [m.project_views(lat, calibs, grid, crange, reserved_cus=reserved) for m, lat in work]
-        else:
-            main = _lib.current_stream(grid.device)
-            side = _streams(grid.device)
-            lins = []
-            for i, (m, lat) in enumerate(work):
-                st = main if i % N_STREAMS == 0 else side[i % N_STREAMS - 1]
-                if st is not main:
-                    st.wait_stream(main)  # the inputs (and last step's consumers of recycled memory) are ready
-                with torch.cuda.stream(st):
-                    lins.append(m.project_views(lat, calibs, grid, crange, reserved_cus=reserved))
-                if st is not main:
-                    lins[-1].record_stream(main)
-            for st in side:
-                main.wait_stream(st)
-        lin8, lin16, lin32 = lins
-        ortho = _ScaleViewSum.apply(lin8, lin16, lin32, vfa8.collapse.bias, vfa16.collapse.bias, vfa32.collapse.bias)
-    else:  # a rank without cameras (8 GPUs, 7 cameras) contributes zeros
-        ortho = torch.zeros((length * width, vfa8.collapse.out_features), dtype=torch.float32, device=grid.device)
+    else:  # which kernels the frame runs through: vfa_op.frame_route ("Routes of a frame")
+        maps = integrals if integrals is not None else (lat8, lat16, lat32)
+        route = vfa_op.frame_route(mods3, n, maps, (calibs, grid), from_integrals=integrals is not None)
+        ortho = vfa_op.run_frame(route, mods3, maps, calibs, grid, crange, reserved_cus=reserved, from_integrals=integrals is not None)
     c_out = vfa8.collapse.out_features
     op = dist.ReduceOp.MAX if view_reduce == "max" else dist.ReduceOp.SUM
     if distributed in ("async", "async_reduce"):

@@ -29,16 +29,15 @@ from .utils import project  # noqa: F401  (re-exported like the reference module
 EPSILON = 1e-6
 MAXIMUM_AREA_RATIO = 0.3
 
-# bound on the transient voxel-feature buffer (n_views, cells, nl*C) fp32; larger grids are chunked over cells
+# The switches `frame_route` reads when a frame is routed (`_route_switches`); what each route launches and which shipped
+# configuration runs it by default: DESIGN.md 4.0, "Routes of a frame".
+# bound on the transient voxel-feature buffer (n_views, cells, nl*C) fp32; larger grids are chunked over cells (`_cell_chunks`)
 VOX_BYTES_LIMIT = int(os.environ.get("VFA_AMD_VOX_BYTES", str(8 << 30)))
 # fused pooling + fp32-MFMA collapse kernel (256 -> 256 channels, no gradient needed): never materialises vox, so it is
 # the memory-lean path for very large grids.  On MI355X it runs at the speed of pooling kernel + library GEMM (fp32 MFMA
 # is clock/power-bound either way), so it is opt-in: VFA_AMD_FUSED=1.
 USE_FUSED = os.environ.get("VFA_AMD_FUSED", "0") == "1"
-# `collapse` on single-layer grids (K = N = 256) when no gradient is needed: "mfma_bf16" (default) = the hand-written
-# bf16-split MFMA kernel fused with bias, ReLU and the view sum (include/vfa_hip.h: vfa_collapse_relu_sum_f32);
-# on multi-layer grids and in training (K = nl*C a multiple of 128, N = 256) the product alone runs as the K-looped MFMA
-# tile GEMM `vfa_collapse_gemm_f32` in front of the epilogue kernels; "library" = fp32 library GEMM everywhere.
+# "mfma_bf16" (default) = the hand-written MFMA kernels; "library" = fp32 library GEMM everywhere
 COLLAPSE_KERNEL = os.environ.get("VFA_AMD_COLLAPSE", "mfma_bf16")
 # Arithmetic of the product in the fused frame kernels (VFA_FLAG_TERMS): 2 (default) = two fp16 pieces per operand with a
 # power-of-two scale, three MFMA products -- the error of an fp32 sgemm, i.e. the arithmetic width of the reference's nn.Linear
@@ -46,14 +45,16 @@ COLLAPSE_KERNEL = os.environ.get("VFA_AMD_COLLAPSE", "mfma_bf16")
 # product kernels (`vfa_collapse_gemm_f32`, `vfa_collapse_relu_sum_f32`: the training backward's mask, VFA_AMD_PIPE=0 paths) have the
 # bf16 forms only and read 2 / 6 as 3.
 COLLAPSE_TERMS = int(os.environ.get("VFA_AMD_COLLAPSE_TERMS", "2"))
-# Inference on single-layer grids with C = 256: "1" (default) = geometry once per frame (`vfa_frame_records_f32`) + ONE
-# persistent kernel for pooling, collapse, bias, ReLU and the view / scale sums (`vfa_pool_collapse_relu_sum_f32`): the voxel
-# features never reach HBM.  "0" = pooling kernel -> vox in HBM -> MFMA collapse kernel, per scale (the round-1 path).
+# single-layer grids: the serial per-frame kernel (route "fused") ...
 FUSED_POOL = os.environ.get("VFA_AMD_FUSED_POOL", "1") == "1"
-# With FUSED_POOL off: "1" (default) = the per-frame box records also feed the standalone LDS-window pooling kernel
-# (`vfa_pool_windows_f32`, voxel features bit-identical to `vfa_project_gather_f32`) in front of the MFMA collapse kernel;
-# "0" = the round-1 pooling kernels that project every box themselves.
+# ... and with it off, the LDS-window pooling kernel in front of the MFMA collapse kernel (route "window")
 WINDOW_POOL = os.environ.get("VFA_AMD_WINDOW_POOL", "1") == "1"
+# any layer count: the pipelined per-frame kernel (routes "pipe", "pipe_batch") ...
+PIPE = os.environ.get("VFA_AMD_PIPE", "1") == "1"
+# ... on single-layer grids too ("0": the serial kernel keeps them, `FUSED_POOL`)
+PIPE_SINGLE_LAYER = os.environ.get("VFA_AMD_PIPE_SINGLE_LAYER", "0") == "1"
+# training: the forward of a frame is the per-frame kernel, the backward recomputes (route "train"); "0" = `vox` / `lin` saved by autograd
+FUSED_TRAIN = os.environ.get("VFA_AMD_FUSED_TRAIN", "1") == "1"
 
 
 def _conv_kind(args):
@@ -171,12 +172,144 @@ def _one_frame_module_set(mods, n_views):
                     and tuple(m.args.image_size) == tuple(m0.args.image_size) for m in mods))
 
 
+def _hand_written():
+    """The library is opted out (``COLLAPSE_KERNEL``): the hand-written product kernels run."""
+    return COLLAPSE_KERNEL != "library"
+
+
+def _frame_kernels_cover(mods, n_views):
+    """Module set / camera count the per-frame kernels cover (gradients or not)."""
+    return _hand_written() and _one_frame_module_set(mods, n_views)
+
+
+def _wants_grad(mods, tensors=()):
+    """Autograd is on and a ``collapse`` weight or bias of ``mods`` or one of ``tensors`` (features, calibs, grid; None is skipped)
+    requires a gradient."""
+    return torch.is_grad_enabled() and (any(m.collapse.weight.requires_grad or m.collapse.bias.requires_grad for m in mods)
+                                        or any(t is not None and t.requires_grad for t in tensors))
+
+
 def fused_frame_ok(mods, n_views, mode="fused"):
     """The per-frame-records inference paths (``mode`` "fused": one persistent kernel for everything behind the integral
     images; "window": LDS-window pooling kernel + MFMA collapse kernel per scale) cover these projector modules (one per
     feature scale) for this many cameras."""
     on = FUSED_POOL if mode == "fused" else (WINDOW_POOL and not FUSED_POOL)
-    return bool(on and COLLAPSE_KERNEL != "library" and _one_frame_module_set(mods, n_views) and mods[0].num_grid_layer == 1)
+    return bool(on and _frame_kernels_cover(mods, n_views) and mods[0].num_grid_layer == 1)
+
+
+def pipe_frame_ok(mods, n_views, tensors=()):
+    """The pipelined per-frame inference path covers these projector modules (one per feature scale; any layer count, the
+    same for all) for this many cameras, and no gradient is wanted (of the weights, biases or ``tensors``: pass the features and
+    the geometry -- calibs, grid -- of the call)."""
+    return bool((mods[0].num_grid_layer > 1 or PIPE_SINGLE_LAYER) and pipe_frames_ok(mods, n_views, tensors))
+
+
+def pipe_frames_ok(mods, n_views, tensors=()):
+    """``pipe_frame_ok`` for a batch of frames of one rig (``pipe_frames``): single-layer grids included -- the batched launch exists
+    in the pipelined kernel only.  ``tensors``: the features and the geometry (calibs, grid) of the call -- no gradient may be wanted."""
+    return bool(PIPE and _frame_kernels_cover(mods, n_views) and not _wants_grad(mods, tensors))
+
+
+def producer_train_ok(mods, n_views):
+    """The fused training node can take the producer's integral images for this module set / camera count (the gates of
+    ``fused_train_ok`` that do not look at ``requires_grad``): a per-frame kernel is switched on for the layer count."""
+    return bool(FUSED_TRAIN and _frame_kernels_cover(mods, n_views) and (PIPE or (mods[0].num_grid_layer == 1 and FUSED_POOL)))
+
+
+def fused_train_ok(mods, n_views, features, geometry=()):
+    """Gradients are wanted -- of the weights, biases, ``features`` or the ``geometry`` tensors (calibs, grid) -- and the fused
+    per-frame kernels cover the forward."""
+    return _wants_grad(mods, tuple(features) + tuple(geometry)) and producer_train_ok(mods, n_views)
+
+
+def mfma_gemm_ok(K, N):
+    """The K-looped MFMA GEMM covers this `collapse` shape (any layer count at C = 256)."""
+    return _hand_written() and N == 256 and K % 128 == 0
+
+
+ROUTES = ("zeros", "train", "pipe_batch", "pipe", "fused", "window", "scale_mfma", "scale_autograd")
+
+
+def _route_switches():
+    """Every switch ``frame_route`` and its predicates read, as it stands now (tests and bench.py set them): the key of a memoised route."""
+    return (PIPE, PIPE_SINGLE_LAYER, FUSED_POOL, WINDOW_POOL, COLLAPSE_KERNEL, FUSED_TRAIN, VOX_BYTES_LIMIT)
+
+
+def frame_route(mods, n_views, maps=(), geometry=(), *, from_integrals=False, frames=None):
+    """The path of one frame (one of ``ROUTES``): a pure function of the switches, the modules, the camera count,
+    ``torch.is_grad_enabled()`` and the ``requires_grad`` of weights, biases, ``maps`` (lateral maps; integral images with
+    ``from_integrals``) and ``geometry`` (calibs, grid: its shape bounds "window").  ``frames``: "pipe_batch" where one launch covers a
+    batch of frames of one rig, else the route of each frame.  Integral images have no per-scale path: they raise where none applies."""
+    tensors = tuple(maps) + tuple(geometry)
+    if frames is not None and pipe_frames_ok(mods, n_views, tensors):
+        return "pipe_batch"
+    if from_integrals:
+        if fused_train_ok(mods, n_views, maps, geometry):
+            return "train"
+        assert n_views > 0 and (pipe_frame_ok(mods, n_views) or fused_frame_ok(mods, n_views)), \
+            "integral-image inputs need a per-frame path"
+        assert not (torch.is_grad_enabled() and any(i.requires_grad for i in maps)), \
+            "integral-image inputs with gradients need the fused training node (fused_train_ok)"
+        return "pipe" if pipe_frame_ok(mods, n_views) else "fused"
+    if n_views == 0:
+        return "zeros"
+    if fused_train_ok(mods, n_views, maps, geometry):
+        return "train"
+    if pipe_frame_ok(mods, n_views, tensors):
+        return "pipe"
+    if not all(m.mfma_collapse_ok(geometry=tensors) for m in mods):
+        return "scale_autograd"
+    if fused_frame_ok(mods, n_views):
+        return "fused"
+    grid = geometry[1] if len(geometry) > 1 else None
+    vox_bytes = 0 if grid is None else n_views * grid.shape[-3] * grid.shape[-2] * 1024  # (n, L*W, 256) fp32 of one scale
+    if fused_frame_ok(mods, n_views, "window") and vox_bytes <= VOX_BYTES_LIMIT:
+        return "window"
+    return "scale_mfma"
+
+
+def run_frame(route, mods, maps, calibs, grid, crange, out=None, accumulate=False, reserved_cus=0, from_integrals=False):
+    """The driver of ``route`` (``frame_route``) -> the frame's (L*W, 256) map, (B, L*W, 256) for "pipe_batch".  ``maps`` as in
+    ``frame_route``.  The inference routes write ``out`` (allocated here when None) or add to it (``accumulate``)."""
+    feats, integrals = (None, maps) if from_integrals else (list(maps), None)
+    if route == "train":
+        return fused_frame_train(mods, feats, calibs, grid, crange, reserved_cus=reserved_cus, integrals=integrals)
+    if route == "pipe_batch":
+        return pipe_frames(mods, feats, calibs, grid, maps[0].shape[0] // calibs.shape[0], crange, out=out, accumulate=accumulate,
+                           reserved_cus=reserved_cus, integrals=integrals)
+    if route == "scale_autograd":
+        from . import aggregate
+        return aggregate.scale_autograd_frame(mods, feats, calibs, grid, crange, reserved_cus)
+    if out is None:
+        out = torch.empty((grid.shape[-3] * grid.shape[-2], mods[0].collapse.out_features), dtype=torch.float32, device=grid.device)
+        accumulate = False
+    if route in ("pipe", "fused"):
+        (pipe_frame if route == "pipe" else fused_frame)(mods, feats, calibs, grid, crange, out=out, accumulate=accumulate, reserved_cus=reserved_cus, integrals=integrals)
+    elif route == "window":
+        window_frame(mods, feats, calibs, grid, crange, out=out, accumulate=accumulate, reserved_cus=reserved_cus)
+    elif route == "scale_mfma":
+        for i, (m, f) in enumerate(zip(mods, feats)):
+            m.project_sum(f, calibs, grid, crange, out=out, accumulate=accumulate or i > 0, reserved_cus=reserved_cus)
+    elif route != "zeros":
+        raise ValueError(f"run_frame: {route!r} is none of {ROUTES}")
+    elif not accumulate:
+        out.zero_()
+    return out
+
+
+def _frame_prelude(m0, grid, device):
+    """What every driver reads off its first module and the grid: conv_kind, (img_w, img_h) -- the path uses image_size[::-1]
+    (vfa_op.py:75) --, (L, W) -- (cells,) of a flat grid --, z_layers and corner_off on ``device``."""
+    conv_kind = _conv_kind(m0.args)
+    img_h, img_w = (float(v) for v in m0.args.image_size)
+    return (conv_kind, (img_w, img_h), tuple(grid.shape[-3:-1]), *m0._kernel_geometry(device))
+
+
+def _cell_chunks(n_cells, bytes_per_cell):
+    """(begin, count) of the cell ranges that keep a transient buffer of ``bytes_per_cell`` per cell within ``VOX_BYTES_LIMIT``."""
+    chunk = max(1, min(n_cells, VOX_BYTES_LIMIT // max(bytes_per_cell, 1)))
+    for begin in range(0, n_cells, chunk):
+        yield begin, min(chunk, n_cells - begin)
 
 
 def fused_frame(mods, features, calibs, grid, crange=(-1, 0.95), out=None, accumulate=False, reserved_cus=0, integrals=None):
@@ -189,12 +322,8 @@ def fused_frame(mods, features, calibs, grid, crange=(-1, 0.95), out=None, accum
     if integrals is not None:
         features = [i.permute(0, 3, 1, 2)[:, :, 1:-1, 1:-1] for i in integrals]  # views: only their shapes are read below
     _lib.require_device(calibs, grid, *features)
-    m0 = mods[0]
-    conv_kind = _conv_kind(m0.args)
-    img_h, img_w = (float(v) for v in m0.args.image_size)  # the path uses image_size[::-1] (vfa_op.py:75)
-    length, width = grid.shape[-3], grid.shape[-2]
     dev = features[0].device
-    z_layers, corner_off = m0._kernel_geometry(dev)
+    conv_kind, (img_w, img_h), (length, width), z_layers, corner_off = _frame_prelude(mods[0], grid, dev)
     with torch.no_grad():
         # geometry (camera + grid only) on a second HIP stream, beside the integral images (bandwidth-bound, feature maps only)
         cur = _lib.current_stream(dev)
@@ -232,28 +361,8 @@ def fused_frame(mods, features, calibs, grid, crange=(-1, 0.95), out=None, accum
                                  reserved_cus=reserved_cus, stage="main")
 
 
-# Inference with C = 256 on ANY number of z-layers: "1" (default) = geometry once per frame (`vfa_pipe_records_f32`) + ONE persistent
-# producer / consumer kernel (`vfa_pipe_collapse_relu_sum_f32`: pooling waves beside matrix waves, the accumulators of four views
-# in registers over all layers); "0" = the older paths (FUSED_POOL on single-layer grids, vox through HBM on multi-layer ones).
-PIPE = os.environ.get("VFA_AMD_PIPE", "1") == "1"
-# ... on single-layer grids too ("0": the serial kernel of vfa_fused.hip keeps them, `FUSED_POOL`)
-PIPE_SINGLE_LAYER = os.environ.get("VFA_AMD_PIPE_SINGLE_LAYER", "0") == "1"
 # bound on the per-frame geometry workspace of the pipeline path; larger frames are processed in bands of grid rows
 PIPE_WS_LIMIT = int(os.environ.get("VFA_AMD_PIPE_WS_BYTES", str(3 << 30)))
-
-
-def pipe_frame_ok(mods, n_views, tensors=()):
-    """The pipelined per-frame inference path covers these projector modules (one per feature scale; any layer count, the
-    same for all) for this many cameras, and no gradient is wanted (of the weights, biases or ``tensors``: pass the features and
-    the geometry -- calibs, grid -- of the call)."""
-    if not (PIPE and COLLAPSE_KERNEL != "library" and _one_frame_module_set(mods, n_views)):
-        return False
-    if mods[0].num_grid_layer == 1 and not PIPE_SINGLE_LAYER:
-        return False
-    if not torch.is_grad_enabled():
-        return True
-    params = [p for m in mods for p in (m.collapse.weight, m.collapse.bias)] + [t for t in tensors if t is not None]
-    return not any(p.requires_grad for p in params)
 
 
 def pipe_frame(mods, features, calibs, grid, crange=(-1, 0.95), out=None, accumulate=False, reserved_cus=0, integrals=None,
@@ -272,15 +381,13 @@ def pipe_frame(mods, features, calibs, grid, crange=(-1, 0.95), out=None, accumu
         features = [i.permute(0, 3, 1, 2)[:, :, 1:-1, 1:-1] for i in integrals]  # views: only their shapes are read below
     _lib.require_device(calibs, grid, *features)
     m0 = mods[0]
-    conv_kind = _conv_kind(m0.args)
-    img_h, img_w = (float(v) for v in m0.args.image_size)  # the path uses image_size[::-1] (vfa_op.py:75)
+    dev = features[0].device
+    conv_kind, (img_w, img_h), lw, z_layers, corner_off = _frame_prelude(m0, grid, dev)
     if grid.dim() < 3:
         raise ValueError("pipe_frame needs the grid as (L, W, 3) or (1, L, W, 3): the tiles follow its rows and columns")
-    grid = grid.reshape(grid.shape[-3], grid.shape[-2], 3)
-    length, width = grid.shape[0], grid.shape[1]
-    dev = features[0].device
+    length, width = lw
+    grid = grid.reshape(length, width, 3)
     n, nl, ns = calibs.shape[0], m0.num_grid_layer, len(mods)
-    z_layers, corner_off = m0._kernel_geometry(dev)
     if out is None:
         out = torch.empty((length * width, 256), dtype=torch.float32, device=dev)
         accumulate = False
@@ -336,17 +443,6 @@ def pipe_frame(mods, features, calibs, grid, crange=(-1, 0.95), out=None, accumu
     return out
 
 
-def pipe_frames_ok(mods, n_views, tensors=()):
-    """``pipe_frame_ok`` for a batch of frames of one rig (``pipe_frames``): single-layer grids included -- the batched launch exists
-    in the pipelined kernel only.  ``tensors``: the features and the geometry (calibs, grid) of the call -- no gradient may be wanted."""
-    if not (PIPE and COLLAPSE_KERNEL != "library" and _one_frame_module_set(mods, n_views)):
-        return False
-    if not torch.is_grad_enabled():
-        return True
-    params = [p for m in mods for p in (m.collapse.weight, m.collapse.bias)] + [t for t in tensors if t is not None]
-    return not any(p.requires_grad for p in params)
-
-
 def pipe_frames(mods, features, calibs, grid, n_frames, crange=(-1, 0.95), out=None, accumulate=False, reserved_cus=0, integrals=None,
                 terms=None):
     """``pipe_frame`` for a batch of ``n_frames`` frames of ONE static rig, in one launch of the pipelined kernel per band:
@@ -363,15 +459,14 @@ def pipe_frames(mods, features, calibs, grid, n_frames, crange=(-1, 0.95), out=N
         features = [i.permute(0, 3, 1, 2)[:, :, 1:-1, 1:-1] for i in integrals]  # views: only their shapes are read below
     _lib.require_device(calibs, grid, *features)
     m0 = mods[0]
-    conv_kind = _conv_kind(m0.args)
-    img_h, img_w = (float(v) for v in m0.args.image_size)
+    dev = features[0].device
+    conv_kind, (img_w, img_h), lw, z_layers, corner_off = _frame_prelude(m0, grid, dev)
     if grid.dim() < 3:
         raise ValueError("pipe_frames needs the grid as (L, W, 3) or (1, L, W, 3): the tiles follow its rows and columns")
     if calibs.dim() != 3:
         raise ValueError(f"pipe_frames takes one rig for the whole batch: calibs (n, 3, 4), got {tuple(calibs.shape)}")
-    grid = grid.reshape(grid.shape[-3], grid.shape[-2], 3)
-    length, width = grid.shape[0], grid.shape[1]
-    dev = features[0].device
+    length, width = lw
+    grid = grid.reshape(length, width, 3)
     n, nl, ns = calibs.shape[0], m0.num_grid_layer, len(mods)
     if B < 0 or any(f.shape[0] != B * n for f in features):
         raise ValueError(f"pipe_frames: every scale needs {B} x {n} maps (frame-major), got {[tuple(f.shape) for f in features]}")
@@ -382,7 +477,6 @@ def pipe_frames(mods, features, calibs, grid, n_frames, crange=(-1, 0.95), out=N
         raise ValueError("pipe_frames: out must be a contiguous fp32 (B, L*W, 256) tensor")
     if B == 0 or length * width == 0:
         return out
-    z_layers, corner_off = m0._kernel_geometry(dev)
     feat_hws = [tuple(f.shape[-2:]) for f in features]
     rows = length
     while rows > 4 and ops.pipe_batch_workspace_bytes(B, n, rows, width, nl, ns) > PIPE_WS_LIMIT:
@@ -510,16 +604,6 @@ def _pipe_state(dev, key, ws_bytes, n_bands, layout=None):
     return st
 
 
-# Training: "1" (default) = the forward of a frame is the fused per-frame kernel (no voxel features, no pre-activations kept);
-# the backward recomputes them scale by scale from the lateral maps.  "0" = the unfused kernels with `vox` / `lin` saved by autograd.
-FUSED_TRAIN = os.environ.get("VFA_AMD_FUSED_TRAIN", "1") == "1"
-
-
-def _frame_kernels_cover(mods, n_views):
-    """Module set / camera count the fused per-frame kernels cover (gradients or not)."""
-    return COLLAPSE_KERNEL != "library" and _one_frame_module_set(mods, n_views)
-
-
 class _FusedFrameTrain(torch.autograd.Function):
     """The whole frame as ONE autograd node (reference: the camera loop vfanet.py:64-82 around VFA.forward vfa_op.py:61-125,
     trained through by trainer.py:26, 41).
@@ -549,9 +633,9 @@ class _FusedFrameTrain(torch.autograd.Function):
                 integrals.absmax = list(tensors[3 * ns:4 * ns])
             else:
                 integrals = ops.integral_images([l.detach() for l in lats])  # kept: the backward pools from them again
-            piped = pipe_frame_ok(mods, n)
-            frame = pipe_frame if piped else fused_frame
-            out = frame(mods, None, calibs, grid, crange, reserved_cus=reserved_cus, integrals=integrals)
+            piped = frame_route(mods, n) == "pipe"  # (else the serial kernel, also where FUSED_POOL keeps inference off it)
+            out = run_frame("pipe" if piped else "fused", mods, integrals, calibs, grid, crange, reserved_cus=reserved_cus,
+                            from_integrals=True)
         # (the feature statistics too: with them the backward repeats the forward's fp16 product -- scales, shifts, order -- and its ReLU
         # mask is the forward's bit for bit)
         f16 = (COLLAPSE_TERMS if piped else _fused_terms()) in (0, 2)
@@ -568,15 +652,12 @@ class _FusedFrameTrain(torch.autograd.Function):
         weights = ctx.saved_tensors[2 + ns:2 + 2 * ns]
         biases = ctx.saved_tensors[2 + 2 * ns:2 + 3 * ns]
         stats = ctx.saved_tensors[2 + 3 * ns:2 + 4 * ns] if f16 else (None,) * ns
-        m0 = mods[0]
-        conv_kind = _conv_kind(m0.args)
-        img_h, img_w = (float(v) for v in m0.args.image_size)
         n = calibs.shape[0]
         dev = grad_out.device
+        conv_kind, (img_w, img_h), _, z_layers, corner_off = _frame_prelude(mods[0], grid, dev)
         grid_flat = grid.reshape(-1, 3).to(dtype=torch.float32).contiguous()
         cal = calibs.reshape(n, 12).to(dtype=torch.float32).contiguous()
-        z_layers, corner_off = m0._kernel_geometry(dev)
-        n_cells, nl, C = grid_flat.shape[0], m0.num_grid_layer, 256
+        n_cells, nl, C = grid_flat.shape[0], mods[0].num_grid_layer, 256
         grad_out = grad_out.contiguous()
         g_lats, g_ws, g_bs = [], [], []
         # the geometry gradient (calibs, grid): every scale's share added into one buffer, scales and chunks in order
@@ -597,15 +678,13 @@ class _FusedFrameTrain(torch.autograd.Function):
                 per_cell = n * nl * C * 4 * 2  # vox and d vox
                 if need_lat and ops.deterministic_mode():  # + the workspace of the deterministic scatter (linear in the cells)
                     per_cell += -(-ops.det_workspace_bytes(n, nl, 1024, C, integral.shape[1] - 2, integral.shape[2] - 2) // 1024)
-                chunk = max(1, min(n_cells, VOX_BYTES_LIMIT // max(per_cell, 1)))
                 # the sliver shifts the forward's geometry pass gave this scale's items (serial kernel: per (view, tile); pipelined: per
                 # tile over views and layers): the recomputed product scales its rows the same way
                 shifts = None
                 if stat is not None and grid.dim() >= 3:
                     shifts = ops.sliver_shifts(cal, grid, z_layers, corner_off, conv_kind, (img_w, img_h),
                                                (integral.shape[1] - 2, integral.shape[2] - 2), not piped, crange)
-                for begin in range(0, n_cells, chunk):
-                    count = min(chunk, n_cells - begin)
+                for begin, count in _cell_chunks(n_cells, per_cell):
                     vox = ops.project_gather(integral, cal, grid_flat, z_layers, corner_off, conv_kind, (img_w, img_h), crange,
                                              cell_begin=begin, cell_count=count)
                     # (the product again, as the two-piece bf16 MFMA tile GEMM -- the unfused product kernels have the bf16 forms only:
@@ -722,35 +801,13 @@ def fused_frame_train(mods, features, calibs, grid, crange=(-1, 0.95), reserved_
     return _FusedFrameTrain.apply(calibs, grid, tuple(crange), (tuple(mods), from_integrals), reserved_cus, *tensors)
 
 
-def producer_train_ok(mods, n_views):
-    """The fused training node can take the producer's integral images for this module set / camera count (the gates of
-    ``fused_train_ok`` that do not look at ``requires_grad``)."""
-    return (FUSED_TRAIN and _frame_kernels_cover(mods, n_views)
-            and (PIPE or (mods[0].num_grid_layer == 1 and FUSED_POOL)))
-
-
-def fused_train_ok(mods, n_views, features, geometry=()):
-    """Gradients are wanted -- of the weights, biases, ``features`` or the ``geometry`` tensors (calibs, grid) -- and the fused
-    per-frame kernels cover the forward."""
-    if not (FUSED_TRAIN and torch.is_grad_enabled() and _frame_kernels_cover(mods, n_views)):
-        return False
-    if not (PIPE or (mods[0].num_grid_layer == 1 and FUSED_POOL)):
-        return False
-    tensors = [p for m in mods for p in (m.collapse.weight, m.collapse.bias)] + [f for f in features if f is not None]
-    return any(t.requires_grad for t in tensors) or any(t is not None and t.requires_grad for t in geometry)
-
-
 def window_frame(mods, features, calibs, grid, crange=(-1, 0.95), out=None, accumulate=False, reserved_cus=0):
     """Same contract as ``fused_frame``, as separate kernels per scale: geometry once per frame (``ops.frame_records``), then
     per scale the integral images, the LDS-window pooling kernel (``ops.pool_windows``: voxel features in HBM, bit-exact) and
     the MFMA collapse + bias + ReLU + view-sum kernel (``ops.collapse_relu_sum``)."""
     _lib.require_device(calibs, grid, *features)
-    m0 = mods[0]
-    conv_kind = _conv_kind(m0.args)
-    img_h, img_w = (float(v) for v in m0.args.image_size)
-    length, width = grid.shape[-3], grid.shape[-2]
     dev = features[0].device
-    z_layers, corner_off = m0._kernel_geometry(dev)
+    conv_kind, (img_w, img_h), (length, width), z_layers, corner_off = _frame_prelude(mods[0], grid, dev)
     n = calibs.shape[0]
     if out is None:
         out = torch.empty((length * width, 256), dtype=torch.float32, device=dev)
@@ -765,11 +822,6 @@ def window_frame(mods, features, calibs, grid, crange=(-1, 0.95), out=None, accu
             ops.collapse_relu_sum(vox, m.layer_major_weight(), m.collapse.bias, out=out, accumulate=accumulate or k > 0,
                                   terms=_unfused_terms(), reserved_cus=reserved_cus)
     return out
-
-
-def mfma_gemm_ok(K, N):
-    """The K-looped MFMA GEMM covers this `collapse` shape (any layer count at C = 256)."""
-    return COLLAPSE_KERNEL != "library" and N == 256 and K % 128 == 0
 
 
 class _BiasReluSum(torch.autograd.Function):
@@ -838,15 +890,12 @@ class VFA(nn.Module):
         vox . collapse.weight^T, WITHOUT bias and ReLU (the epilogue kernels add them while summing views).
         """
         _lib.require_device(features, calibs, grid)
-        conv_kind = _conv_kind(self.args)
-        img_h, img_w = (float(v) for v in self.args.image_size)  # the path uses image_size[::-1] (vfa_op.py:75)
+        conv_kind, (img_w, img_h), _, z_layers, corner_off = _frame_prelude(self, grid, features.device)
         n, C, Hf, Wf = features.shape
         if C != self.channel:
             raise ValueError(f"feature has {C} channels, VFA was built for {self.channel}")
-        dev = features.device
         grid_flat = grid.reshape(-1, 3).to(dtype=torch.float32).contiguous()
         calibs = calibs.reshape(n, 12).to(dtype=torch.float32).contiguous()
-        z_layers, corner_off = self._kernel_geometry(dev)
         # (+ the width of the ground grid: the backward scatter works on patches of 4 x 8 cells)
         geom = (conv_kind, img_w, img_h, float(crange[0]), float(crange[1]), int(grid.shape[-2]) if grid.dim() >= 3 else 0)
         n_cells, nl = grid_flat.shape[0], self.num_grid_layer
@@ -854,20 +903,15 @@ class VFA(nn.Module):
         if n_cells == 0 or n == 0:
             return features.new_zeros((n, n_cells, self.collapse.out_features))
         integral = _IntegralImage.apply(features)
-        needs_grad = torch.is_grad_enabled() and (features.requires_grad or self.collapse.weight.requires_grad
-                                                  or calibs.requires_grad or grid_flat.requires_grad)
-        if USE_FUSED and not needs_grad and C == 256 and self.collapse.out_features == 256:
+        if USE_FUSED and not _wants_grad([self], (features, calibs, grid_flat)) and C == 256 and self.collapse.out_features == 256:
             # inference: pooling feeds the fp32-MFMA collapse product through LDS, vox never reaches HBM
             w_t = self.layer_major_weight().t().contiguous()
             return ops.project_collapse(integral, calibs, grid_flat, z_layers, corner_off, w_t, conv_kind,
                                         (img_w, img_h), (geom[3], geom[4]))
         w_lm = self.layer_major_weight()
         use_mfma = mfma_gemm_ok(nl * C, self.collapse.out_features)
-        per_cell = n * nl * C * 4
-        chunk = max(1, min(n_cells, VOX_BYTES_LIMIT // max(per_cell, 1)))
         outs = []
-        for begin in range(0, n_cells, chunk):
-            count = min(chunk, n_cells - begin)
+        for begin, count in _cell_chunks(n_cells, n * nl * C * 4):
             vox = _BoxPool.apply(integral, calibs, grid_flat, z_layers, corner_off, geom, begin, count)
             if use_mfma:
                 lin = _CollapseGemm.apply(vox.view(n * count, nl * C), w_lm.contiguous(), reserved_cus)
@@ -879,12 +923,8 @@ class VFA(nn.Module):
     def mfma_collapse_ok(self, features=None, geometry=()):
         """True when the inference-only bf16-split MFMA kernel (`vfa_collapse_relu_sum_f32`) covers this module and no gradient
         is wanted (of the weights, bias, ``features`` or the ``geometry`` tensors: calibs, grid)."""
-        if COLLAPSE_KERNEL == "library" or self.num_grid_layer * self.channel != 256 or self.collapse.out_features != 256:
-            return False
-        if not torch.is_grad_enabled():
-            return True
-        params = (self.collapse.weight, self.collapse.bias) + (() if features is None else (features,)) + tuple(geometry)
-        return not any(p is not None and p.requires_grad for p in params)
+        return (_hand_written() and self.num_grid_layer * self.channel == 256 and self.collapse.out_features == 256
+                and not _wants_grad([self], (features, *geometry)))
 
     def project_sum(self, features, calibs, grid, crange=(-1, 0.95), out=None, accumulate=False, reserved_cus=0):
         """Inference path of one scale, all cameras: ``out (L*W, C_out) (+)= sum_v relu(collapse(vox_v))``.
@@ -893,14 +933,12 @@ class VFA(nn.Module):
         (``ops.collapse_relu_sum``): neither ``lin`` nor a separate epilogue pass exists.  Needs ``mfma_collapse_ok``.
         """
         _lib.require_device(features, calibs, grid)
-        conv_kind = _conv_kind(self.args)
-        img_h, img_w = (float(v) for v in self.args.image_size)
+        conv_kind, (img_w, img_h), _, z_layers, corner_off = _frame_prelude(self, grid, features.device)
         n, C, Hf, Wf = features.shape
         if C != self.channel:
             raise ValueError(f"feature has {C} channels, VFA was built for {self.channel}")
         grid_flat = grid.reshape(-1, 3).to(dtype=torch.float32).contiguous()
         calibs = calibs.reshape(n, 12).to(dtype=torch.float32).contiguous()
-        z_layers, corner_off = self._kernel_geometry(features.device)
         n_cells, nl = grid_flat.shape[0], self.num_grid_layer
         if out is None:
             out = torch.empty((n_cells, self.collapse.out_features), dtype=torch.float32, device=features.device)
@@ -909,21 +947,13 @@ class VFA(nn.Module):
             return out
         if n == 0:
             return out if accumulate else out.zero_()
-        if grid.dim() >= 3 and pipe_frame_ok([self], n, (features,)):
-            return pipe_frame([self], [features], calibs, grid, crange, out=out, accumulate=accumulate, reserved_cus=reserved_cus)
-        if grid.dim() >= 3 and fused_frame_ok([self], n):
-            return fused_frame([self], [features], calibs, grid, crange, out=out, accumulate=accumulate,
-                               reserved_cus=reserved_cus)
-        if grid.dim() >= 3 and fused_frame_ok([self], n, "window") and n * n_cells * C * 4 <= VOX_BYTES_LIMIT:
-            return window_frame([self], [features], calibs, grid, crange, out=out, accumulate=accumulate,
-                                reserved_cus=reserved_cus)
+        route = frame_route([self], n, (features,), (calibs, grid)) if grid.dim() >= 3 else "scale_mfma"
+        if route in ("pipe", "fused", "window"):  # a per-frame kernel covers this scale on its own
+            return run_frame(route, [self], [features], calibs, grid, crange, out=out, accumulate=accumulate, reserved_cus=reserved_cus)
         with torch.no_grad():
             integral = ops.integral_image(features)
             weight = self.layer_major_weight()
-            per_cell = n * nl * C * 4
-            chunk = max(1, min(n_cells, VOX_BYTES_LIMIT // max(per_cell, 1)))
-            for begin in range(0, n_cells, chunk):
-                count = min(chunk, n_cells - begin)
+            for begin, count in _cell_chunks(n_cells, n * nl * C * 4):
                 vox = ops.project_gather(integral, calibs, grid_flat, z_layers, corner_off, conv_kind, (img_w, img_h),
                                          (float(crange[0]), float(crange[1])), cell_begin=begin, cell_count=count)
                 ops.collapse_relu_sum(vox, weight, self.collapse.bias, out=out[begin:begin + count],
@@ -946,9 +976,10 @@ class VFA(nn.Module):
             return lazy.DeferredOrtho([(self, feature, lazy.version_of(feature), calib, lazy.version_of(calib))], grid,
                                       (float(crange[0]), float(crange[1])), (1, self.collapse.out_features, length, width),
                                       feature.device)
-        if grid.dim() >= 3 and fused_train_ok([self], 1, (feature,), (calib, grid)):
-            ortho = fused_frame_train([self], [feature], calib.reshape(1, 3, 4), grid, crange)
-        elif self.mfma_collapse_ok(feature, (calib, grid)) or (grid.dim() >= 3 and pipe_frame_ok([self], 1, (feature, calib, grid))):
+        route = frame_route([self], 1, (feature,), (calib, grid))
+        if route == "train":
+            ortho = run_frame(route, [self], [feature], calib.reshape(1, 3, 4), grid, crange)
+        elif route != "scale_autograd":  # (``project_sum`` finds the per-frame kernel of this scale, if there is one)
             ortho = self.project_sum(feature, calib.reshape(1, 3, 4), grid, crange)
         else:
             lin = self.project_views(feature, calib.reshape(1, 3, 4), grid, crange)
@@ -958,10 +989,10 @@ class VFA(nn.Module):
     def _defer_ok(self):
         """A per-frame inference kernel covers this module on its own (what ``_materialize`` can always fall back to), memoised on the
         switches that decide it."""
-        key = (PIPE, PIPE_SINGLE_LAYER, FUSED_POOL, COLLAPSE_KERNEL, self.num_grid_layer, self.channel, self.collapse.out_features)
+        key = (_route_switches(), self.num_grid_layer, self.channel, self.collapse.out_features)
         cached = getattr(self, "_defer_cache", None)
         if cached is None or cached[0] != key:
-            cached = (key, bool(pipe_frame_ok([self], 1) or fused_frame_ok([self], 1)))
+            cached = (key, frame_route([self], 1) in ("pipe", "fused"))  # (asked with autograd off: see ``forward``)
             self._defer_cache = cached
         return cached[1]
 
@@ -1010,10 +1041,9 @@ def _materialize(terms, grid, crange):
         same_cameras = all(len(cl) == n and all(a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape) for a, b in zip(cl, calib_lists[0]))
                            for cl in calib_lists[1:])
         calibs0 = torch.stack([c.reshape(3, 4) for c in calib_lists[0]]).to(dtype=torch.float32)
-        if same_cameras and pipe_frame_ok(mods, n, feats):
-            pipe_frame(mods, feats, calibs0, grid, crange, out=out)
-        elif same_cameras and fused_frame_ok(mods, n):
-            fused_frame(mods, feats, calibs0, grid, crange, out=out)
+        route = frame_route(mods, n, feats) if same_cameras else None
+        if route in ("pipe", "fused"):
+            run_frame(route, mods, feats, calibs0, grid, crange, out=out)
         else:
             for i, (m, f, cl) in enumerate(zip(mods, feats, calib_lists)):
                 m.project_sum(f, torch.stack([c.reshape(3, 4) for c in cl]).to(dtype=torch.float32), grid, crange, out=out, accumulate=i > 0)
@@ -1023,9 +1053,7 @@ def _materialize(terms, grid, crange):
 def box_parameters(module, calibs, grid, feat_hw, crange=(-1, 0.95)):
     """Stage output for tests / visualisation: box (n,nl,cells,4), area, visible of every view (vfa_op.py:64-106)."""
     _lib.require_device(calibs, grid)
-    conv_kind = _conv_kind(module.args)
-    img_h, img_w = (float(v) for v in module.args.image_size)
-    z_layers, corner_off = module._kernel_geometry(calibs.device)
+    conv_kind, (img_w, img_h), _, z_layers, corner_off = _frame_prelude(module, grid, calibs.device)
     box, area, visible = ops.box_params(calibs, grid.reshape(-1, 3), z_layers, corner_off, conv_kind, (img_w, img_h),
                                         feat_hw, crange)
     return dict(box=box, area=area, visible=visible.bool())
@@ -1052,8 +1080,9 @@ class FrameGeometry:
         _lib.require_device(calibs, grid)
         n = calibs.shape[0]
         with torch.no_grad():  # (inference only: the parameters' requires_grad is not what decides here)
-            self.pipe = pipe_frame_ok(mods, n)
-        if not self.pipe and not fused_frame_ok(mods, n):
+            route = frame_route(mods, n)
+        self.pipe = route == "pipe"
+        if route not in ("pipe", "fused"):
             raise ValueError("FrameGeometry needs a module set the per-frame inference kernels cover (C = 256, one layer count, <= 32 cameras)")
         m0 = mods[0]
         grid3 = grid.reshape(grid.shape[-3], grid.shape[-2], 3)
@@ -1061,9 +1090,7 @@ class FrameGeometry:
         self.mods, self.n, self.nl, self.crange, self.reserved_cus = mods, n, m0.num_grid_layer, crange, int(reserved_cus)
         self.feat_hws = [tuple(int(v) for v in hw) for hw in feat_hws]
         dev = calibs.device
-        z_layers, corner_off = m0._kernel_geometry(dev)
-        conv_kind = _conv_kind(m0.args)
-        img_h, img_w = (float(v) for v in m0.args.image_size)
+        conv_kind, (img_w, img_h), _, z_layers, corner_off = _frame_prelude(m0, grid3, dev)
         with torch.no_grad():
             if self.pipe:
                 self.terms = COLLAPSE_TERMS

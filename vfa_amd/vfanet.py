@@ -189,7 +189,7 @@ class VFANet(nn.Module):
             images, calibs = images[idx], calibs[idx]
         mods3 = [self.vfa8, self.vfa16, self.vfa32]
         if (FUSE_PRODUCER and self.view_reduce == "sum" and not torch.is_grad_enabled() and images.is_cuda and images.shape[0]
-                and (vfa_op.fused_frame_ok(mods3, images.shape[0]) or vfa_op.pipe_frame_ok(mods3, images.shape[0]))):
+                and vfa_op.frame_route(mods3, images.shape[0]) in ("pipe", "fused")):
             return aggregate_views(self.vfa8, self.vfa16, self.vfa32, None, None, None, calibs, grid, (-1, 0.95),
                                    distributed=distributed, integrals=self.lateral_integrals(images))
         if self.producer_train_ok(images):
@@ -213,7 +213,7 @@ class VFANet(nn.Module):
             raise ValueError(f"VFANet: images {tuple(images.shape)} need calibs ({N},3,4) or ({B},{N},3,4), got {tuple(calibs.shape)}")
         mods3 = [self.vfa8, self.vfa16, self.vfa32]
         if (B == 0 or distributed or calibs.dim() == 4 or torch.is_grad_enabled() or self.view_reduce != "sum"
-                or not (images.is_cuda and vfa_op.pipe_frames_ok(mods3, N))):
+                or not (images.is_cuda and vfa_op.frame_route(mods3, N, frames=B) == "pipe_batch")):
             outs = [self.ortho_features(images[b], calibs[b] if calibs.dim() == 4 else calibs, grid, distributed) for b in range(B)]
             return torch.cat(outs, 0) if outs else images.new_zeros(0, 256, grid.shape[-3], grid.shape[-2])
         flat = images.reshape(B * N, *images.shape[2:])
