@@ -737,6 +737,47 @@ int vfa_bev_decode_f32(const float *heatmap, const float *loc_offset, const long
                        int yx_first, void *workspace, size_t workspace_bytes, int *count, float *conf, float *location, int *cell,
                        float *dimension, float *rotation_out, void *stream);
 
+/* ---- a 3x3 convolution at listed cells: the orientation head where it is read ------------------------------------------------
+ *
+ * vfa_conv3x3_at_cells_f32: the dense convolution weight (O, C, 3, 3) * feat, dilation d >= 1, zero padding d ("same"), no bias,
+ * evaluated at k listed cells of each of B frames instead of at all L * W: the same function gathered at the cells, up to the
+ * fp32 summation order.  Stream-ordered, no allocation, no host round trip, no atomics: the same bits on every run.
+ *                                    replaces orient_pred of vfa/model/vfanet.py:53 where decode3d / the CSL loss read it
+ *   feat (B, C, L, W) float32, read through four ELEMENT strides {frame, channel, row, column} >= 0 given as a HOST array: NCHW
+ *   and channels-last storage are taken alike and never copied.  weight (O, C, 3, 3) contiguous, 16-byte aligned.
+ *   cell (B, k) int32, the flat index l * W + w.  An entry outside [0, L * W) -- the decode writes -1 behind a frame's count -- is a
+ *   SKIPPED row: its logits are zeros, its rotation is 0.0f, and no address is formed from it.
+ *   Out, at least one of the two:
+ *   - logits (B, k, O): logits[b, j, o] = sum over the 9 taps t = 3 ty + tx and the C channels of
+ *     weight[o, c, ty, tx] * feat[b, c, l + (ty - 1) d, w + (tx - 1) d]; a tap outside the map contributes nothing.  Products and
+ *     sums are fp32 (v_mfma_f32_16x16x4_f32: an fmaf chain); the two partial sums of an element are added in a fixed order, and
+ *     the logits are the same bits whether or not the rotation is asked for;
+ *   - rotation (B, k): (float)argmax * (float)(pi / 180) by exactly the rule of vfa_bev_decode_f32 (one device function serves
+ *     both: csrc/vfa_rotation.h).  With logits == NULL the logits are staged in `workspace`, the caller's, 4-byte aligned, of
+ *     vfa_conv3x3_at_cells_workspace_bytes(B, k, O) bytes; otherwise the workspace is not looked at.
+ *   Limits and errors: a negative size, C < 1, O < 1, d < 1, a negative stride, a NULL required pointer, neither output, a short
+ *   workspace: VFA_ERR_BAD_ARGUMENT; B * k == 0 returns 0 and writes nothing; C % 32 != 0, a weight that is not 16-byte aligned,
+ *   L * W or B * k >= 2^31 - 16, O > 2^21: VFA_ERR_UNSUPPORTED.
+ *
+ * vfa_conv3x3_at_cells_backward_f32: from d_logits (B, k, O), either or both of
+ *   - d_weight (O, C, 3, 3) = the sum over the rows that are not skipped of d_logits[b, j, o] * tap, one fmaf chain per element in
+ *     ASCENDING row order b * k + j;
+ *   - d_feat (B, C, L, W), contiguous and dense, EVERY element written (zeros where no tap lies).  A location receives the sum
+ *     over the (row, tap) pairs of its frame that lie on it and over o of d_logits * weight.  Several pairs do lie on one
+ *     location (cells exactly d apart in a row, a column or a diagonal; duplicate cells): the location is written once, by its
+ *     lowest pair, which adds the pairs in ascending (row, tap) order and inside a pair o ascending (csrc/vfa_cellconv.h).
+ *   No float atomics, no workspace: both are the same bits on every run.  Skipped rows contribute nothing, whatever their
+ *   d_logits hold.  Errors as for the forward (a NULL d_logits or neither output: VFA_ERR_BAD_ARGUMENT); B * k == 0 writes zeros;
+ *   d_feat with k > VFA_CELLCONV_MAX_ROWS: VFA_ERR_UNSUPPORTED. */
+#define VFA_CELLCONV_MAX_ROWS 1024
+size_t vfa_conv3x3_at_cells_workspace_bytes(int B, int k, int O);
+int vfa_conv3x3_at_cells_f32(const float *feat, const long long *feat_stride, const float *weight, const int *cell, int B, int C, int L,
+                             int W, int O, int k, int dilation, float *logits, float *rotation, void *workspace, size_t workspace_bytes,
+                             void *stream);
+int vfa_conv3x3_at_cells_backward_f32(const float *d_logits, const float *feat, const long long *feat_stride, const float *weight,
+                                      const int *cell, int B, int C, int L, int W, int O, int k, int dilation, float *d_feat,
+                                      float *d_weight, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

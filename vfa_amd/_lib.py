@@ -125,6 +125,9 @@ SIGNATURES = {
     "vfa_bev_decode_workspace_bytes": [_c_int, _c_int, _c_int, _c_int],
     "vfa_bev_decode_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float,
                            _c_float, _c_float, _vp, _c_int, _vp, _c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "vfa_conv3x3_at_cells_workspace_bytes": [_c_int, _c_int, _c_int],
+    "vfa_conv3x3_at_cells_f32": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_size_t, _vp],
+    "vfa_conv3x3_at_cells_backward_f32": [_vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp],
 }
 
 _lib = None

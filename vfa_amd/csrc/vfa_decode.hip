@@ -9,7 +9,7 @@
 //      - collect: the candidates with key >= threshold, at most k, into LDS (slots from an LDS counter: any order), padded with zero
 //        keys to a power of two and ordered by a bitonic network.  Keys are unique, so the order does not depend on the slots;
 //      - decode: the waves take the selected cells in turn; lane 0 does the box arithmetic, the 64 lanes reduce the cell's rotation
-//        logits by (sigmoid value, lowest index).  Rows from the frame's count on are written as zeros, cell -1.
+//        logits by (sigmoid value, lowest index): vfa_rotation.h.  Rows from the frame's count on are written as zeros, cell -1.
 // fp32, one operation per reference operation, no contraction (-ffp-contract=off); expf is the device's.  No atomics on memory:
 // every call gives the same bits.  A NaN logit is no candidate (the NMS writes 0 for it) and never wins the arg-max.
 #include <hip/hip_runtime.h>
@@ -17,10 +17,12 @@
 
 #include "vfa_decode.h"
 #include "vfa_hip.h"
+#include "vfa_rotation.h"
 
 namespace {
 
 using namespace vfa_decode;
+using vfa_rotation::sigmoid;
 
 constexpr int kThreads = 1024, kWaves = kThreads / 64;
 
@@ -36,8 +38,6 @@ struct DecodeArgs {
     int *count, *cell;
     float *conf, *location, *dimension, *rotation;
 };
-
-__device__ __forceinline__ float sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 __global__ __launch_bounds__(kThreads) void bev_decode_kernel(const DecodeArgs a)
 {
@@ -129,19 +129,8 @@ __global__ __launch_bounds__(kThreads) void bev_decode_kernel(const DecodeArgs a
         }
         if (three_d) {
             const float *o = a.rot + b * a.rot_s.frame + l * a.rot_s.row + w * a.rot_s.col;
-            float best = -1.0f; // below every sigmoid; a NaN never passes `>`
-            int best_at = INT32_MAX;
-            for (int c = lane; c < a.n_rot; c += 64) { // (ascending c: the first of equal values stays)
-                const float v = sigmoid(o[c * a.rot_s.chan]);
-                if (v > best) { best = v; best_at = c; }
-            }
-#pragma unroll
-            for (int step = 32; step > 0; step >>= 1) {
-                const float v = __shfl_xor(best, step, 64);
-                const int at = __shfl_xor(best_at, step, 64);
-                if (v > best || (v == best && at < best_at)) { best = v; best_at = at; }
-            }
-            if (lane == 0) a.rotation[row] = (float)(best_at == INT32_MAX ? 0 : best_at) * 0.017453292519943295f; // torch.deg2rad
+            const float rotation = vfa_rotation::wave_rotation(o, a.rot_s.chan, a.n_rot, lane); // (the rule: vfa_rotation.h)
+            if (lane == 0) a.rotation[row] = rotation;
         }
     }
 }

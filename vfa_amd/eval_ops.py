@@ -22,7 +22,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 
 
 def sort_vertices(vertices, mask, num_valid):
@@ -513,8 +513,12 @@ class BEVDecoder:
         ``conf (B, k)``; ``location (B, k, 3)``; ``cell (B, k)`` int32, the flat index ``l * W + w``; in 3D ``dimension (B, k, 3)``
         and ``rotation (B, k)``.  Frame ``b``'s detections are rows ``0 .. count[b] - 1``: those ``batch_decode`` gives for it (cells
         with ``conf > cls_thresh`` among the top k), by confidence descending, EQUAL confidences by ascending cell (``torch.topk``
-        leaves that order open); the rows behind them are zeros with ``cell`` -1.  ``ValueError``: ``cls_thresh < 0`` (the
-        equivalence with top-k-then-threshold needs it), ``topk`` outside 1 .. 1024, a 3D base without ``dimension_mean``."""
+        leaves that order open); the rows behind them are zeros with ``cell`` -1.  In place of ``rotation``, ``pred`` may carry
+        ``rotation_head = (feature (B, C, L, W), weight (R, C, 3, 3), dilation)`` (``VFANet.heads(..., rotation_at="detections")``):
+        the orientation head is then evaluated at the selected cells only (``vfa_conv3x3_at_cells_f32``, the same arg-max rule),
+        still without a host wait or an allocation that depends on a value; every other output is unchanged.
+        ``ValueError``: ``cls_thresh < 0`` (the equivalence with top-k-then-threshold needs it), ``topk`` outside 1 .. 1024, a 3D base
+        without ``dimension_mean``."""
         three_d = self.base in ("MultiviewC", "MVM3D")
         if not float(cls_thresh) >= 0:
             raise ValueError(f"decode_fused: cls_thresh must be >= 0, got {cls_thresh}")
@@ -522,7 +526,8 @@ class BEVDecoder:
             raise ValueError(f"decode_fused: topk must be in 1 .. {DECODE_MAX_TOPK}, got {self.topk}")
         if three_d and self.dimension_mean is None:
             raise ValueError(f"decode_fused: base {self.base} decodes 3D boxes and needs dimension_mean")
-        names = ("heatmap", "loc_offset") + (("dim_offset", "rotation") if three_d else ())
+        at_cells = three_d and "rotation_head" in pred and "rotation" not in pred
+        names = ("heatmap", "loc_offset") + ((("dim_offset",) if at_cells else ("dim_offset", "rotation")) if three_d else ())
         _lib.require_device(*(pred[n] for n in names))
         heat = pred["heatmap"].to(torch.float32).contiguous()
         if heat.dim() != 4 or heat.shape[1] != 1:
@@ -541,8 +546,11 @@ class BEVDecoder:
         n_rot = 0
         if three_d:
             dim, dim_stride = head("dim_offset", 3)
-            rot, rot_stride = head("rotation", 0)
-            n_rot = rot.shape[3]
+            if at_cells:  # the library call decodes one zero logit read through zero strides; the rotation is written below
+                rot, rot_stride, n_rot = torch.zeros(1, dtype=torch.float32, device=dev), (ctypes.c_longlong * 4)(0, 0, 0, 0), 1
+            else:
+                rot, rot_stride = head("rotation", 0)
+                n_rot = rot.shape[3]
             if n_rot < 1:
                 raise ValueError("decode_fused: rotation needs at least one channel")
             mean = (ctypes.c_float * 3)(*[float(m) for m in self.dimension_mean])
@@ -562,6 +570,11 @@ class BEVDecoder:
                   float(self.world_size[0]), float(self.world_size[1]), mean, int(self.base == "Wildtrack" and not three_d),
                   _lib.ptr(ws), ws_bytes, _lib.ptr(out["count"]), _lib.ptr(out["conf"]), _lib.ptr(out["location"]),
                   _lib.ptr(out["cell"]), _lib.ptr(out.get("dimension")), _lib.ptr(out.get("rotation")), _lib.current_stream_handle())
+        if at_cells and not empty:
+            feat, weight, dilation = pred["rotation_head"]
+            if feat.dim() != 4 or (feat.shape[0], feat.shape[2], feat.shape[3]) != (B, L, W):
+                raise ValueError(f"decode_fused: rotation_head's feature must be (B, C, L, W) = ({B}, C, {L}, {W}), got {tuple(feat.shape)}")
+            out["rotation"] = ops.conv3x3_at_cells_forward(feat, weight, out["cell"], dilation, want_logits=False, want_rotation=True)[1]
         return out
 
     @staticmethod

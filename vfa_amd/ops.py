@@ -1107,3 +1107,60 @@ def pipe_batch_balance(workspace, n_frames, n_views, grid_lw, n_layers, n_scales
     L, W = grid_lw
     _launch("vfa_pipe_batch_balance_f32", int(n_frames), int(n_views), int(L), int(W), int(n_layers), int(n_scales), int(reserved_cus),
             0 if reset else 1, _lib.ptr(workspace), workspace.numel(), _lib.current_stream_handle())
+
+
+def _cells_operands(name, feat, weight, cells):
+    _lib.require_device(feat, weight, cells)
+    if feat.dtype != torch.float32 or feat.dim() != 4:
+        raise ValueError(f"{name}: feat must be float32 (B, C, L, W), got {feat.dtype} {tuple(feat.shape)}")
+    B, C, L, W = feat.shape
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (C, 3, 3):
+        raise ValueError(f"{name}: weight must be (O, {C}, 3, 3), got {tuple(weight.shape)}")
+    if cells.dtype != torch.int32 or cells.dim() != 2 or cells.shape[0] != B:
+        raise ValueError(f"{name}: cells must be int32 ({B}, k), got {cells.dtype} {tuple(cells.shape)}")
+    return _f32c(weight), cells.contiguous(), (ctypes.c_longlong * 4)(*feat.stride()), (B, C, L, W, weight.shape[0], cells.shape[1])
+
+
+def conv3x3_at_cells_forward(feat, weight, cells, dilation=1, want_logits=True, want_rotation=False):
+    """``F.conv2d(feat, weight, padding=dilation, dilation=dilation)`` at the listed cells only, no autograd
+    (``vfa_conv3x3_at_cells_f32``).  feat (B,C,L,W) float32 read through its strides (NCHW or channels-last, never copied), weight
+    (O,C,3,3), cells (B,k) int32 flat ``l * W + w`` -> (logits (B,k,O) or None, rotation (B,k) or None).  A cell outside
+    ``[0, L * W)`` is a skipped row: zeros.  rotation: the decode's arg-max rule on the logits."""
+    weight, cells, stride, (B, C, L, W, O, k) = _cells_operands("conv3x3_at_cells", feat, weight, cells)
+    if not (want_logits or want_rotation):
+        raise ValueError("conv3x3_at_cells: nothing is asked for")
+    dev = feat.device
+    logits = torch.empty((B, k, O), dtype=torch.float32, device=dev) if want_logits else None
+    rotation = torch.empty((B, k), dtype=torch.float32, device=dev) if want_rotation else None
+    ws_bytes = 0 if want_logits else _lib.lib().vfa_conv3x3_at_cells_workspace_bytes(B, k, O)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    _launch("vfa_conv3x3_at_cells_f32", _lib.ptr(feat), stride, _lib.ptr(weight), _lib.ptr(cells), B, C, L, W, O, k, int(dilation),
+            _lib.ptr(logits), _lib.ptr(rotation), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(), tag=(B, C, L, W, O, k))
+    return logits, rotation
+
+
+def conv3x3_at_cells_backward(grad_logits, feat, weight, cells, dilation=1, want_feat=True, want_weight=True):
+    """Backward of ``conv3x3_at_cells_forward``: grad_logits (B,k,O) -> (d_feat (B,C,L,W) contiguous, dense, or None; d_weight
+    (O,C,3,3) or None) (``vfa_conv3x3_at_cells_backward_f32``: no float atomics, the same bits on every run)."""
+    weight, cells, stride, (B, C, L, W, O, k) = _cells_operands("conv3x3_at_cells_backward", feat, weight, cells)
+    _lib.require_device(grad_logits)
+    if tuple(grad_logits.shape) != (B, k, O):
+        raise ValueError(f"conv3x3_at_cells_backward: grad_logits must be ({B}, {k}, {O}), got {tuple(grad_logits.shape)}")
+    grad_logits = _f32c(grad_logits)
+    d_feat = torch.empty((B, C, L, W), dtype=torch.float32, device=feat.device) if want_feat else None
+    d_weight = torch.empty((O, C, 3, 3), dtype=torch.float32, device=feat.device) if want_weight else None
+    if want_feat or want_weight:
+        _launch("vfa_conv3x3_at_cells_backward_f32", _lib.ptr(grad_logits), _lib.ptr(feat), stride, _lib.ptr(weight), _lib.ptr(cells),
+                B, C, L, W, O, k, int(dilation), _lib.ptr(d_feat), _lib.ptr(d_weight), _lib.current_stream_handle(),
+                tag=(B, C, L, W, O, k))
+    return d_feat, d_weight
+
+
+def conv3x3_at_cells(feat, weight, cells, dilation=1, want_rotation=False):
+    """A 3x3 convolution (zero padding = dilation, no bias) evaluated only at ``cells (B, k)`` int32 (flat ``l * W + w``; an entry
+    outside the map, such as the decode's -1, is a skipped row of zeros) -> ``logits (B, k, O)``, or ``(logits, rotation (B, k))``.
+    Differentiable with respect to ``feat`` and ``weight`` (one autograd node on the two entry points, ``vfa_op._ConvAtCells``);
+    skipped rows get no gradient, the rotation is not differentiable."""
+    from . import vfa_op  # (vfa_op imports this module)
+    logits, rotation = vfa_op._ConvAtCells.apply(feat, weight, cells, int(dilation), bool(want_rotation))
+    return (logits, rotation) if want_rotation else logits

@@ -839,6 +839,27 @@ class _BiasReluSum(torch.autograd.Function):
         return ops.relu_mask_backward(grad_out, lin, bias)
 
 
+class _ConvAtCells(torch.autograd.Function):
+    """(logits (B,k,O), rotation (B,k) or None) = a 3x3 convolution of feat (B,C,L,W) at cells (B,k) only (``ops.conv3x3_at_cells``).
+    The backward gives a dense d feat (zeros where no tap lies) and d weight; rows whose cell lies outside the map get none."""
+
+    @staticmethod
+    def forward(ctx, feat, weight, cells, dilation, want_rotation):
+        logits, rotation = ops.conv3x3_at_cells_forward(feat, weight, cells, dilation, want_rotation=want_rotation)
+        ctx.save_for_backward(feat, weight, cells)
+        ctx.dilation = dilation
+        if rotation is not None:
+            ctx.mark_non_differentiable(rotation)
+        return logits, rotation
+
+    @staticmethod
+    def backward(ctx, grad_logits, _grad_rotation):
+        feat, weight, cells = ctx.saved_tensors
+        d_feat, d_weight = ops.conv3x3_at_cells_backward(grad_logits, feat, weight, cells, ctx.dilation,
+                                                         want_feat=ctx.needs_input_grad[0], want_weight=ctx.needs_input_grad[1])
+        return d_feat, d_weight, None, None, None
+
+
 class VFA(nn.Module):
     def __init__(self, channel, grid_height=160, cube_size=(25, 25, 32), feat_scale=1, args=None):
         super().__init__()

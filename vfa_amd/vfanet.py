@@ -223,13 +223,20 @@ class VFANet(nn.Module):
         lat8, lat16, lat32 = self.laterals(flat)
         return aggregate_views(self.vfa8, self.vfa16, self.vfa32, lat8, lat16, lat32, calibs, grid, (-1, 0.95), frames=B)
 
-    def forward(self, images, calibs, grid, visualize=False, visualize_ortho=False, distributed=False):
+    def forward(self, images, calibs, grid, visualize=False, visualize_ortho=False, distributed=False, rotation_at=None):
         """images (N,3,iH,iW), calibs (N,3,4), grid (1,L,W,3) -> dict like the reference (vfanet.py:141-149).
-        images (B,N,3,iH,iW): a batch of B frames, calibs (N,3,4) or (B,N,3,4); the heads run at batch B."""
+        images (B,N,3,iH,iW): a batch of B frames, calibs (N,3,4) or (B,N,3,4); the heads run at batch B.
+        ``rotation_at``: evaluate the orientation head only where it is read (``heads``)."""
         if visualize or visualize_ortho:
             self._visualize(images, calibs, grid, boxes=visualize_ortho)
         topdown = self.ortho_features(images, calibs, grid, distributed)
-        return self.heads(topdown)
+        return self.heads(topdown, rotation_at)
+
+    def detect(self, images, calibs, grid, decoder, cls_thresh):
+        """Inference from images to ``BEVDecoder.decode_fused``'s detections without the dense orientation map: the heads with
+        ``rotation_at="detections"``, then the decode, which evaluates ``orient_pred`` at the cells it selected."""
+        with torch.no_grad():
+            return decoder.decode_fused(self.forward(images, calibs, grid, rotation_at="detections"), cls_thresh)
 
     def _visualize(self, images, calibs, grid, boxes=False):
         """Slow matplotlib side path (reference vfanet.py:84-128): per camera, the norms of the three lateral maps, of
@@ -253,11 +260,30 @@ class VFANet(nn.Module):
                 if boxes:
                     self.vfa8.visualize_cube(one[0], calibs[cam], grid)
 
-    def heads(self, topdown):
-        """The BEV heads on the fused map (reference vfanet.py:131-149)."""
+    def heads(self, topdown, rotation_at=None):
+        """The BEV heads on the fused map (reference vfanet.py:131-149).
+
+        ``rotation_at`` (3D only, ``ValueError`` in 2D) evaluates ``orient_pred`` -- the largest layer of the heads, read at a few
+        dozen cells -- only where it is read, on ``ops.conv3x3_at_cells`` instead of a dense convolution; the other heads are the
+        same calls.  ``None``: the dense ``rotation (B, L, W, R)`` of the reference.  ``cells (B, k)`` int32, flat ``l * W + w``
+        (training: the positive cells of the loss, in ascending order the order of ``pred['rotation'][mask]``; an entry outside the
+        map is a row of zeros without gradient): ``rotation_at (B, k, R)`` logits and ``rotation_cells`` instead of ``rotation``,
+        differentiable.  ``"detections"`` (inference): ``rotation_head = (fused feature, orient_pred weight, dilation)``, from which
+        ``BEVDecoder.decode_fused`` takes the rotation at the cells it selects."""
+        if rotation_at is not None and self.mode != "3D":
+            raise ValueError("VFANet.heads: rotation_at needs mode 3D (a 2D model has no orientation head)")
         fused = self.fuse(topdown)
         out = {"heatmap": self.map_classifier(fused), "loc_offset": self.tytx_pred(topdown).permute(0, 2, 3, 1)}
         if self.mode == "3D":
             out["dim_offset"] = self.thtwtl_pred(topdown).permute(0, 2, 3, 1)
-            out["rotation"] = self.orient_pred(fused).permute(0, 2, 3, 1)
+            conv = self.orient_pred[0]
+            if rotation_at is None:
+                out["rotation"] = self.orient_pred(fused).permute(0, 2, 3, 1)
+            elif isinstance(rotation_at, str):
+                if rotation_at != "detections":
+                    raise ValueError(f"VFANet.heads: rotation_at is None, 'detections' or cells (B, k), got {rotation_at!r}")
+                out["rotation_head"] = (fused, conv.weight, conv.dilation[0])
+            else:
+                out["rotation_at"] = ops.conv3x3_at_cells(fused, conv.weight, rotation_at, dilation=conv.dilation[0])
+                out["rotation_cells"] = rotation_at
         return out
