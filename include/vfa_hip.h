@@ -778,6 +778,56 @@ int vfa_conv3x3_at_cells_backward_f32(const float *d_logits, const float *feat, 
                                       const int *cell, int B, int C, int L, int W, int O, int k, int dilation, float *d_feat,
                                       float *d_weight, void *stream);
 
+/* ---- the training targets and the detection loss in the sparse (positive-cell list) form, no host round trip -------------------
+ *
+ * vfa_det_targets_f32: the encode half of ObjectEncoder for B frames of up to K objects, one workgroup per frame.
+ *                                                            replaces vfa/data/encoder.py:152-217 (the three per-object loops)
+ *   location (B, K, loc_width) with loc_width 2 or 3 (x, y[, z]); count (B) int32, clamped to [0, K]; dimension (B, K, 3) and
+ *   rotation (B, K) radians, both or neither (neither: 2D; dim_offset and angle_label are then not written); dimension_mean: 3
+ *   floats on the HOST.  kind: 0 MultiviewC, 1 MultiviewX, 2 Wildtrack (row = coord_x).  The rules (cell, offsets, label,
+ *   duplicates: the later object wins, ascending cell order) are csrc/vfa_loss.h, fp32, one operation per reference operation.
+ *   Out, all written: cells (B, K) int32 = row * W + column, ascending, -1 behind the frame's positives; n_pos (B) int32;
+ *   loc_offset (B, K, 2); dim_offset (B, K, 3) = logf(dimension / mean); angle_label (B, K) int32; zeros behind n_pos.
+ *   DEVIATION: an object outside the map or with a non-finite coordinate is dropped (the reference raises or wraps).
+ *
+ * vfa_det_loss_f32: per frame the reference's terms {heat map focal, location, dimension, angle focal} -> terms (B, 4), their
+ * weighted sum loss (B) (loss.py:66-67, loss_weight: 4 floats on the HOST in the order heat map, location, dimension, angle) and
+ * counts (B, 4) int32 {heat-map positives, negatives, angle positives, negatives} for the backward.  replaces vfa/model/loss.py
+ *   heatmap logits and gt_heatmap through three ELEMENT strides {frame, row, column}; loc_offset (2 channels) / dim_offset (3)
+ *   through four {frame, row, column, channel}; rotation_at (B, k, R) through three {frame, row, channel}; all strides >= 0, HOST
+ *   arrays, nothing copied.  dim_offset == rotation_at == NULL: 2D (two terms, the others 0).  cells / n_pos / loc_target /
+ *   dim_target / angle_label: what vfa_det_targets_f32 writes, (B, k, ...); table (R): exp(-(i - R/2)^2 / (2 sigma^2)) as float32.
+ *   Row r < n_pos[b] of the list is read at cells[b, r]; a cell outside [0, L * W) is skipped.  Heat-map positives are
+ *   gt_heatmap == 1, counted on the dense target.  A frame without positives: 0 for the three sparse terms.
+ *   Two launches; the float32 elements are summed in float64, in a fixed order that depends on (L, W, k, R) only: the same bits
+ *   on every run and in any batch.
+ *   workspace: vfa_det_loss_workspace_bytes(B, L, W) bytes, 8-byte aligned, the caller's.
+ *
+ * vfa_det_loss_backward_f32: coef (B, 4) = d objective / d terms on the device, counts as the forward left them ->
+ *   d_heatmap (B, L, W), d_loc_offset (B, L, W, 2), d_dim_offset (B, L, W, 3) contiguous and dense (zeros off the positive cells),
+ *   d_rotation_at (B, k, R) contiguous (zero rows behind n_pos).  Nothing accumulates: bit-reproducible.
+ *
+ * Limits and errors of the three, decided before anything is launched: a negative size or stride, a NULL required pointer, a
+ * short workspace, loc_width outside {2, 3}, world <= 0: VFA_ERR_BAD_ARGUMENT; K or k > VFA_DET_MAX_OBJECTS, R > VFA_DET_MAX_ROT or
+ * odd, B > 65535, L * W >= 2^31: VFA_ERR_UNSUPPORTED; B == 0 or L * W == 0 (the loss) returns 0 and launches nothing. */
+#define VFA_DET_MAX_OBJECTS 1024
+#define VFA_DET_MAX_ROT 1024
+int vfa_det_targets_f32(const float *location, int loc_width, const int *count, const float *dimension, const float *rotation,
+                        const float *dimension_mean, int B, int K, int L, int W, float world0, float world1, int kind, int *cells,
+                        int *n_pos, float *loc_offset, float *dim_offset, int *angle_label, void *stream);
+size_t vfa_det_loss_workspace_bytes(int B, int L, int W);
+int vfa_det_loss_f32(const float *heatmap, const long long *heat_stride, const float *gt_heatmap, const long long *gt_stride,
+                     const float *loc_offset, const long long *loc_stride, const float *dim_offset, const long long *dim_stride,
+                     const float *rotation_at, const long long *rot_stride, const int *cells, const int *n_pos, const float *loc_target,
+                     const float *dim_target, const int *angle_label, const float *table, const float *loss_weight, int B, int L, int W,
+                     int k, int R, void *workspace, size_t workspace_bytes, float *terms, float *loss, int *counts, void *stream);
+int vfa_det_loss_backward_f32(const float *coef, const float *heatmap, const long long *heat_stride, const float *gt_heatmap,
+                              const long long *gt_stride, const float *loc_offset, const long long *loc_stride, const float *dim_offset,
+                              const long long *dim_stride, const float *rotation_at, const long long *rot_stride, const int *cells,
+                              const int *n_pos, const float *loc_target, const float *dim_target, const int *angle_label,
+                              const float *table, const int *counts, int B, int L, int W, int k, int R, float *d_heatmap,
+                              float *d_loc_offset, float *d_dim_offset, float *d_rotation_at, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

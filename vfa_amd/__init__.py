@@ -9,6 +9,9 @@ from .vfa_op import VFA, FrameGeometry, box_parameters  # noqa: F401
 from .lazy import DeferredOrtho, materialize  # noqa: F401
 from .aggregate import (aggregate_views, all_reduce_ortho, all_reduce_prehead_grads, camera_shard, reduce_ortho,  # noqa: F401
                         reduce_scatter_ortho, row_bands)
+from .loss import (DetTargets, PackedObjects, TargetEncoder, compute_loss2d, compute_loss3d, detection_loss,  # noqa: F401
+                   pack_objects)
 
-__all__ = ["VFA", "FrameGeometry", "aggregate_views", "all_reduce_ortho", "all_reduce_prehead_grads", "camera_shard", "box_parameters", "make_grid", "materialize", "project",
+__all__ = ["DetTargets", "PackedObjects", "TargetEncoder", "compute_loss2d", "compute_loss3d", "detection_loss", "pack_objects",
+           "VFA", "FrameGeometry", "aggregate_views", "all_reduce_ortho", "all_reduce_prehead_grads", "camera_shard", "box_parameters", "make_grid", "materialize", "project",
            "reduce_ortho", "reduce_scatter_ortho", "row_bands"]

@@ -1164,3 +1164,108 @@ def conv3x3_at_cells(feat, weight, cells, dilation=1, want_rotation=False):
     from . import vfa_op  # (vfa_op imports this module)
     logits, rotation = vfa_op._ConvAtCells.apply(feat, weight, cells, int(dilation), bool(want_rotation))
     return (logits, rotation) if want_rotation else logits
+
+
+def _det_f32(name, **tensors):
+    """The detection-loss entry points take float32 operands on the device; anything else is refused, not converted."""
+    _lib.require_device(*tensors.values())
+    for key, t in tensors.items():
+        if t is not None and t.dtype != torch.float32:
+            raise _lib.VFAHipError(f"{name}: {key} must be float32, got {t.dtype} (unsupported)")
+
+
+def _strides(t, dims):
+    return None if t is None else (ctypes.c_longlong * len(dims))(*[t.stride(d) for d in dims])
+
+
+def det_targets(location, count, dimension=None, rotation=None, dimension_mean=None, world_size=(1.0, 1.0), grid_lw=(1, 1), kind=0):
+    """``vfa_det_targets_f32``: location (B, K, 2|3), count (B) int32 and in 3D dimension (B, K, 3), rotation (B, K) ->
+    (cells (B, K) int32, n_pos (B) int32, loc_offset (B, K, 2), dim_offset (B, K, 3) | None, angle_label (B, K) int32 | None).
+    One launch, no host wait."""
+    _det_f32("det_targets", location=location, dimension=dimension, rotation=rotation)
+    _lib.require_device(count)
+    if location.dim() != 3 or count.dtype != torch.int32 or count.shape != location.shape[:1]:
+        raise ValueError(f"det_targets: location (B, K, 2|3) and count (B) int32, got {tuple(location.shape)}, {count.dtype} {tuple(count.shape)}")
+    B, K, width = location.shape
+    three_d = dimension is not None or rotation is not None
+    if three_d and (dimension is None or rotation is None or dimension_mean is None or tuple(dimension.shape) != (B, K, 3)
+                    or tuple(rotation.shape) != (B, K)):
+        raise ValueError("det_targets: 3D needs dimension (B, K, 3), rotation (B, K) and dimension_mean (3)")
+    dev = location.device
+    location, count = location.contiguous(), count.contiguous()
+    cells = torch.empty((B, K), dtype=torch.int32, device=dev)
+    n_pos = torch.empty((B,), dtype=torch.int32, device=dev)
+    loc_offset = torch.empty((B, K, 2), dtype=torch.float32, device=dev)
+    dim_offset = torch.empty((B, K, 3), dtype=torch.float32, device=dev) if three_d else None
+    label = torch.empty((B, K), dtype=torch.int32, device=dev) if three_d else None
+    mean = (ctypes.c_float * 3)(*[float(v) for v in dimension_mean]) if three_d else None
+    _launch("vfa_det_targets_f32", _lib.ptr(location), int(width), _lib.ptr(count), _lib.ptr(dimension.contiguous() if three_d else None),
+            _lib.ptr(rotation.contiguous() if three_d else None), mean, B, K, int(grid_lw[0]), int(grid_lw[1]), float(world_size[0]),
+            float(world_size[1]), int(kind), _lib.ptr(cells), _lib.ptr(n_pos), _lib.ptr(loc_offset), _lib.ptr(dim_offset), _lib.ptr(label),
+            _lib.current_stream_handle(), tag=(B, K))
+    return cells, n_pos, loc_offset, dim_offset, label
+
+
+def _det_loss_operands(name, heatmap, gt_heatmap, loc, dim, rot, cells, n_pos, loc_t, dim_t, label, table):
+    _det_f32(name, heatmap=heatmap, gt_heatmap=gt_heatmap, loc_offset=loc, dim_offset=dim, rotation_at=rot, loc_target=loc_t,
+             dim_target=dim_t, table=table)
+    _lib.require_device(cells, n_pos, label)
+    if heatmap.dim() != 4 or heatmap.shape[1] != 1:
+        raise ValueError(f"{name}: heatmap must be (B, 1, L, W), got {tuple(heatmap.shape)}")
+    B, _, L, W = heatmap.shape
+    k = cells.shape[1]
+    three_d = dim is not None
+    R = rot.shape[2] if three_d else 0
+    if tuple(gt_heatmap.shape) != (B, L, W) or tuple(loc.shape) != (B, L, W, 2) or tuple(cells.shape) != (B, k) or tuple(n_pos.shape) != (B,):
+        raise ValueError(f"{name}: gt_heatmap ({B}, {L}, {W}), loc_offset ({B}, {L}, {W}, 2), cells ({B}, k), n_pos ({B}); got "
+                         f"{tuple(gt_heatmap.shape)}, {tuple(loc.shape)}, {tuple(cells.shape)}, {tuple(n_pos.shape)}")
+    if cells.dtype != torch.int32 or n_pos.dtype != torch.int32 or tuple(loc_t.shape) != (B, k, 2):
+        raise ValueError(f"{name}: cells / n_pos int32 and loc_target ({B}, {k}, 2)")
+    if three_d and (rot is None or tuple(dim.shape) != (B, L, W, 3) or tuple(rot.shape) != (B, k, R) or tuple(dim_t.shape) != (B, k, 3)
+                    or tuple(label.shape) != (B, k) or label.dtype != torch.int32 or tuple(table.shape) != (R,)):
+        raise ValueError(f"{name}: 3D needs dim_offset ({B}, {L}, {W}, 3), rotation_at ({B}, {k}, R), dim_target ({B}, {k}, 3), "
+                         f"angle_label ({B}, {k}) int32 and table (R)")
+    if any(s < 0 for t in (heatmap, gt_heatmap, loc, dim, rot) if t is not None for s in t.stride()):
+        raise _lib.VFAHipError(f"{name}: negative strides are not supported")
+    ptrs = [_lib.ptr(heatmap), _strides(heatmap, (0, 2, 3)), _lib.ptr(gt_heatmap), _strides(gt_heatmap, (0, 1, 2)), _lib.ptr(loc),
+            _strides(loc, (0, 1, 2, 3)), _lib.ptr(dim), _strides(dim, (0, 1, 2, 3)), _lib.ptr(rot), _strides(rot, (0, 1, 2)),
+            _lib.ptr(cells.contiguous()), _lib.ptr(n_pos.contiguous()), _lib.ptr(loc_t.contiguous()),
+            _lib.ptr(dim_t.contiguous() if three_d else None), _lib.ptr(label.contiguous() if three_d else None),
+            _lib.ptr(table.contiguous() if three_d else None)]
+    return ptrs, (B, L, W, k, R)
+
+
+def det_loss_forward(heatmap, gt_heatmap, loc, dim, rot, cells, n_pos, loc_t, dim_t, label, table, loss_weight=(1.0, 1.0, 1.0, 1.0)):
+    """``vfa_det_loss_f32``, no autograd: -> (terms (B, 4) = heat map, location, dimension, angle; loss (B); counts (B, 4) int32).
+    Heads are read through their strides (never copied); two launches, no host wait."""
+    ptrs, (B, L, W, k, R) = _det_loss_operands("det_loss", heatmap, gt_heatmap, loc, dim, rot, cells, n_pos, loc_t, dim_t, label, table)
+    dev = heatmap.device
+    terms = torch.zeros((B, 4), dtype=torch.float32, device=dev) if L * W == 0 else torch.empty((B, 4), dtype=torch.float32, device=dev)
+    loss = torch.zeros((B,), dtype=torch.float32, device=dev) if L * W == 0 else torch.empty((B,), dtype=torch.float32, device=dev)
+    counts = torch.zeros((B, 4), dtype=torch.int32, device=dev) if L * W == 0 else torch.empty((B, 4), dtype=torch.int32, device=dev)
+    ws_bytes = _lib.lib().vfa_det_loss_workspace_bytes(B, L, W)
+    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
+    w = list(loss_weight) + [1.0] * (4 - len(loss_weight))
+    _launch("vfa_det_loss_f32", *ptrs, (ctypes.c_float * 4)(*[float(v) for v in w]), B, L, W, k, R, _lib.ptr(ws), ws_bytes,
+            _lib.ptr(terms), _lib.ptr(loss), _lib.ptr(counts), _lib.current_stream_handle(), tag=(B, L, W, k, R))
+    return terms, loss, counts
+
+
+def det_loss_backward(coef, counts, heatmap, gt_heatmap, loc, dim, rot, cells, n_pos, loc_t, dim_t, label, table):
+    """``vfa_det_loss_backward_f32``: coef (B, 4) = d objective / d terms -> (d_heatmap (B, 1, L, W), d_loc_offset (B, L, W, 2),
+    d_dim_offset (B, L, W, 3) | None, d_rotation_at (B, k, R) | None), contiguous, every element written."""
+    ptrs, (B, L, W, k, R) = _det_loss_operands("det_loss_backward", heatmap, gt_heatmap, loc, dim, rot, cells, n_pos, loc_t, dim_t, label,
+                                                table)
+    _det_f32("det_loss_backward", coef=coef)
+    _lib.require_device(counts)
+    if tuple(coef.shape) != (B, 4) or tuple(counts.shape) != (B, 4) or counts.dtype != torch.int32:
+        raise ValueError(f"det_loss_backward: coef ({B}, 4) float32 and counts ({B}, 4) int32")
+    dev, three_d = heatmap.device, dim is not None
+    make = torch.zeros if L * W == 0 else torch.empty
+    d_heat = make((B, 1, L, W), dtype=torch.float32, device=dev)
+    d_loc = make((B, L, W, 2), dtype=torch.float32, device=dev)
+    d_dim = make((B, L, W, 3), dtype=torch.float32, device=dev) if three_d else None
+    d_rot = make((B, k, R), dtype=torch.float32, device=dev) if three_d else None
+    _launch("vfa_det_loss_backward_f32", _lib.ptr(coef.contiguous()), *ptrs, _lib.ptr(counts.contiguous()), B, L, W, k, R, _lib.ptr(d_heat),
+            _lib.ptr(d_loc), _lib.ptr(d_dim), _lib.ptr(d_rot), _lib.current_stream_handle(), tag=(B, L, W, k, R))
+    return d_heat, d_loc, d_dim, d_rot
