@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import REPO
+from native_common import ABI_VERSION, declared_parameters
 
 
 @pytest.fixture(scope="module")
@@ -24,6 +25,19 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(?:int|size_t)\s+(vfa_\w+)\s*\(", text)))
 
 
+def test_binding_has_the_declared_number_of_arguments_for_every_symbol():
+    """Every function of include/vfa_hip.h, not a feature's handful: the declaration and ``_lib.SIGNATURES`` agree in the number
+    of parameters.  With the two tests below (exported, bound) this is what the per-feature modules used to repeat for their own
+    symbols."""
+    from vfa_amd import _lib
+    declared = declared_parameters()
+    assert sorted(declared) == _declared_symbols() and len(declared) >= 78    # the full declarations were all found
+    assert declared["vfa_abi_version"] == 0 == len(_lib.SIGNATURES["vfa_abi_version"])
+    for name, count in declared.items():
+        assert name in _lib.SIGNATURES, f"{name} is not bound in _lib.SIGNATURES"
+        assert count == len(_lib.SIGNATURES[name]), f"{name}: {count} parameters declared, {len(_lib.SIGNATURES[name])} bound"
+
+
 def test_header_declares_the_expected_entry_points():
     syms = _declared_symbols()
     assert "vfa_project_gather_f32" in syms and "vfa_integral_image_f32" in syms
@@ -34,14 +48,14 @@ def test_library_exports_every_declared_symbol(built_lib):
     lib = ctypes.CDLL(built_lib)
     for name in _declared_symbols():
         assert hasattr(lib, name), f"{name} declared in include/vfa_hip.h but not exported"
-    assert lib.vfa_abi_version() == 9
+    assert lib.vfa_abi_version() == ABI_VERSION
     assert not hasattr(lib, "vfa_set_option")  # since ABI v2: tuning choices are per-call flags, the library keeps no state
 
 
 def test_python_binding_covers_every_declared_symbol(built_lib):
     from vfa_amd import _lib
     assert sorted(_lib.SIGNATURES) == _declared_symbols()
-    assert _lib.lib().vfa_abi_version() == _lib.ABI_VERSION
+    assert _lib.lib().vfa_abi_version() == _lib.ABI_VERSION == ABI_VERSION
 
 
 def test_code_object_targets_gfx950(built_lib):

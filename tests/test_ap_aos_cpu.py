@@ -1,9 +1,7 @@
-"""The AP/AOS metric without a GPU: the ABI of the new entry points, the float64 tail of the metric against the reference's
+"""The AP/AOS metric without a GPU (the ABI of its entry points: tests/test_abi.py): the float64 tail of the metric against the reference's
 recorded match tables (tests/golden/ap_aos_mc.npz, generated from the reference by tests/golden/make_ap_aos.py), the margins the
 fixtures promise, the ``vfa.evaluation.pyeval.evaluateAPAOS`` alias and the refusals of the host wrappers."""
-import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -12,8 +10,8 @@ import pytest
 import torch
 
 from conftest import REPO, golden_path
+from native_common import write_checkout
 
-NEW_SYMBOLS = ("vfa_iou3d_f32", "vfa_iou3d_frames_f32")
 THRESHOLDS = (0.75, 0.5, 0.25)
 
 
@@ -21,22 +19,6 @@ THRESHOLDS = (0.75, 0.5, 0.25)
 def built_lib():
     from vfa_amd import build
     return build.build()
-
-
-def test_new_entry_points_are_declared_exported_and_bound(built_lib):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "vfa_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\bint\s+(vfa_\w+)\s*\(", text))
-    lib = ctypes.CDLL(built_lib)
-    from vfa_amd import _lib
-    for name in NEW_SYMBOLS:
-        assert name in declared, f"{name} is not declared in include/vfa_hip.h"
-        assert hasattr(lib, name), f"{name} is not exported by the library"
-        assert name in _lib.SIGNATURES
-    # arguments of the declaration and of the binding agree in number
-    for name in NEW_SYMBOLS:
-        args = re.search(r"\bint\s+" + name + r"\s*\((.*?)\)\s*;", text, flags=re.S).group(1)
-        assert len(args.split(",")) == len(_lib.SIGNATURES[name]), name
-    assert lib.vfa_abi_version() == 9 and _lib.ABI_VERSION == 9
 
 
 def test_ap_aos_tail_reproduces_the_reference_from_its_match_rows():
@@ -123,30 +105,22 @@ def test_fixtures_keep_their_margins():
     assert (p["ref_iou3d"][p["kind"] == "disjoint"] == 0).all() and np.isfinite(p["ref_iou3d"]).all()
 
 
-def _reference_shaped_checkout(root):
-    """A stand-in for the reference checkout behind compat/ (the technique of tests/test_host_cpu.py): the layout the alias
-    package extends, each module a line or two written here."""
-    files = {
-        "vfa/__init__.py": "",
-        "vfa/evaluation/__init__.py": "",
-        "vfa/evaluation/evaluate.py": "from .pyeval.evaluateAPAOS import evaluateDetectionAPAOS\n",
-        "vfa/evaluation/pyeval/__init__.py": "",
-        "vfa/evaluation/pyeval/evaluateAPAOS.py": "ORIGIN = 'checkout'\n\n\ndef evaluateDetectionAPAOS(a, b):\n    return ORIGIN\n",
-        "vfa/evaluation/pyeval/CLEAR_MOD_HUN.py": "ORIGIN = 'checkout'\n",
-        "vfa/evaluation/pyeval/cuda_op/__init__.py": "",
-        "vfa/evaluation/pyeval/cuda_op/cuda_ext.py": "import sort_vertices\n\nbound = sort_vertices.sort_vertices_forward\n",
-        "vfa/evaluation/pyeval/IoU.py": "from .cuda_op.cuda_ext import bound\n",
-    }
-    for rel, text in files.items():
-        path = root / rel
-        path.parent.mkdir(parents=True, exist_ok=True)
-        path.write_text(text)
-    return str(root)
+CHECKOUT_FILES = {  # a stand-in for the reference checkout behind compat/ (native_common.write_checkout)
+    "vfa/__init__.py": "",
+    "vfa/evaluation/__init__.py": "",
+    "vfa/evaluation/evaluate.py": "from .pyeval.evaluateAPAOS import evaluateDetectionAPAOS\n",
+    "vfa/evaluation/pyeval/__init__.py": "",
+    "vfa/evaluation/pyeval/evaluateAPAOS.py": "ORIGIN = 'checkout'\n\n\ndef evaluateDetectionAPAOS(a, b):\n    return ORIGIN\n",
+    "vfa/evaluation/pyeval/CLEAR_MOD_HUN.py": "ORIGIN = 'checkout'\n",
+    "vfa/evaluation/pyeval/cuda_op/__init__.py": "",
+    "vfa/evaluation/pyeval/cuda_op/cuda_ext.py": "import sort_vertices\n\nbound = sort_vertices.sort_vertices_forward\n",
+    "vfa/evaluation/pyeval/IoU.py": "from .cuda_op.cuda_ext import bound\n",
+}
 
 
 @pytest.mark.parametrize("found_through", ["path", "VFA_REFERENCE_ROOT"])
 def test_evaluation_alias_binds_the_metric_and_leaves_the_rest_to_the_checkout(tmp_path, found_through):
-    checkout = _reference_shaped_checkout(tmp_path / "checkout")
+    checkout = write_checkout(tmp_path / "checkout", CHECKOUT_FILES)
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(REPO, "compat"), REPO]))
     env.pop("VFA_REFERENCE_ROOT", None)
     if found_through == "path":

@@ -6,17 +6,15 @@ import ctypes
 import inspect
 import os
 import re
-import subprocess
 from types import SimpleNamespace
 
 import pytest
 import torch
 
 from conftest import REPO
+from native_common import build_harness, run_harness
 
-SYMBOLS = ("vfa_conv3x3_at_cells_workspace_bytes", "vfa_conv3x3_at_cells_f32", "vfa_conv3x3_at_cells_backward_f32")
-HARNESS_SRC = os.path.join(REPO, "tests", "native", "cellconv_harness.cpp")
-GXX = ["g++", "-O1", "-std=c++17", "-Wall"]
+GXX_FLAGS = ["-O1", "-std=c++17", "-Wall"]
 BAD, UNSUPPORTED = 10001, 10002
 
 
@@ -28,41 +26,20 @@ def built_lib():
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("cellconv") / "harness")
-    subprocess.check_call(GXX + ["-o", exe, HARNESS_SRC])
-    return exe
+    return build_harness(tmp_path_factory, "cellconv", "cellconv_harness.cpp", GXX_FLAGS)
 
 
 @pytest.fixture(scope="module")
 def sanitized_harness(tmp_path_factory):
-    """The same stand-alone program (its own ``main``, nothing preloaded) with the address and undefined-behaviour sanitizers."""
-    exe = str(tmp_path_factory.mktemp("cellconv_san") / "harness")
-    subprocess.check_call(GXX + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, HARNESS_SRC])
-    return exe
+    return build_harness(tmp_path_factory, "cellconv", "cellconv_harness.cpp", GXX_FLAGS, sanitized=True)
 
 
-def _run(exe, *args):
-    out = subprocess.run([exe, *args], capture_output=True, text=True, timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
-    return out.stdout
-
-
-def test_entry_points_are_declared_exported_and_bound(built_lib):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "vfa_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(?:int|size_t)\s+(vfa_\w+)\s*\(", text))
-    lib = ctypes.CDLL(built_lib)
-    from vfa_amd import _lib
-    for symbol in SYMBOLS:
-        assert symbol in declared, f"{symbol} is not declared in include/vfa_hip.h"
-        assert hasattr(lib, symbol), f"{symbol} is not exported by the library"
-        assert symbol in _lib.SIGNATURES, f"{symbol} is not bound in _lib.SIGNATURES"
-        args = re.search(r"\b(?:int|size_t)\s+" + symbol + r"\s*\((.*?)\)\s*;", text, flags=re.S).group(1)
-        assert len(args.split(",")) == len(_lib.SIGNATURES[symbol])
+def test_entry_points_are_declared_exported_and_bound():
+    """Declared, exported, bound, the same number of arguments: tests/test_abi.py, for every symbol.  Here: the cap is one number."""
+    text = open(os.path.join(REPO, "include", "vfa_hip.h")).read()
     cap = int(re.search(r"#define\s+VFA_CELLCONV_MAX_ROWS\s+(\d+)", text).group(1))
     shared = open(os.path.join(REPO, "vfa_amd", "csrc", "vfa_cellconv.h")).read()
     assert cap == int(re.search(r"kMaxRows\s*=\s*(\d+)", shared).group(1)) == 1024
-    assert lib.vfa_abi_version() == 9 and _lib.ABI_VERSION == 9          # the change only adds symbols
 
 
 def test_the_rotation_rule_is_stated_once():
@@ -107,7 +84,7 @@ def test_refusals_of_the_entry_points(built_lib):
 
 
 def test_tap_addresses_against_the_enumeration(harness):
-    out = _run(harness, "taps")
+    out = run_harness(harness, "taps")
     taps, outside = (int(v) for v in re.findall(r"(\d+) (?:taps|outside)", out))
     assert taps > 10000 and outside > 1000
 
@@ -116,14 +93,14 @@ def test_tap_addresses_against_the_enumeration(harness):
 def test_ownership_order_against_the_enumeration(harness, seed):
     """Cells a dilation apart in a row, a column and a diagonal, duplicates, ids outside the map, and 300 random lists: every touched
     location has exactly one owner, the lowest pair on it, whose walk lists the location's pairs in ascending (row, tap) order."""
-    out = _run(harness, "owners", str(seed))
+    out = run_harness(harness, "owners", str(seed))
     pairs, shared = (int(v) for v in re.findall(r"(\d+) (?:pairs|shared)", out))
     assert pairs > 10000 and shared > 100
 
 
 def test_integer_logic_under_the_host_sanitizers(sanitized_harness):
-    _run(sanitized_harness, "taps")
-    _run(sanitized_harness, "owners", "4")
+    run_harness(sanitized_harness, "taps")
+    run_harness(sanitized_harness, "owners", "4")
 
 
 def _net(mode="3D"):

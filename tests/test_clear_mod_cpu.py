@@ -3,7 +3,6 @@ vfa_amd/csrc/vfa_assign.h (shared host / device code) compiled with g++ into tes
 brute force and against scipy's per-frame records of tests/golden/clear_mod.npz (generated from the reference by
 tests/golden/make_clear_mod.py), once more under the host sanitizers; the host-only branches of ``clear_mod``; the
 ``vfa.evaluation.pyeval.evaluateDetection`` alias; the refusals of the wrappers; the margins the fixture promises."""
-import ctypes
 import os
 import re
 import subprocess
@@ -15,12 +14,11 @@ import pytest
 import torch
 
 from conftest import REPO, golden_path
+from native_common import build_harness, run_harness, write_checkout
 
-SYMBOL = "vfa_clear_mod_frames_f64"
 TD = 30.0
 SETS = ("demo1", "demo2", "syn")
-HARNESS_SRC = os.path.join(REPO, "tests", "native", "assign_harness.cpp")
-GXX = ["g++", "-O1", "-std=c++17", "-Wall", "-ffp-contract=off"]
+GXX_FLAGS = ["-O1", "-std=c++17", "-Wall", "-ffp-contract=off"]
 
 
 @pytest.fixture(scope="module")
@@ -31,17 +29,12 @@ def built_lib():
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("assign") / "harness")
-    subprocess.check_call(GXX + ["-o", exe, HARNESS_SRC])
-    return exe
+    return build_harness(tmp_path_factory, "assign", "assign_harness.cpp", GXX_FLAGS)
 
 
 @pytest.fixture(scope="module")
 def sanitized_harness(tmp_path_factory):
-    """The same stand-alone program (its own ``main``, nothing preloaded) with the address and undefined-behaviour sanitizers."""
-    exe = str(tmp_path_factory.mktemp("assign_san") / "harness")
-    subprocess.check_call(GXX + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, HARNESS_SRC])
-    return exe
+    return build_harness(tmp_path_factory, "assign", "assign_harness.cpp", GXX_FLAGS, sanitized=True)
 
 
 def _frames_file(path):
@@ -64,32 +57,19 @@ def _frames_file(path):
     return n_frames
 
 
-def _run(exe, *args):
-    out = subprocess.run([exe, *args], capture_output=True, text=True, timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
-    return out.stdout
-
-
-def test_entry_point_is_declared_exported_and_bound(built_lib):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "vfa_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\bint\s+(vfa_\w+)\s*\(", text))
-    lib = ctypes.CDLL(built_lib)
-    from vfa_amd import _lib, eval_ops
-    assert SYMBOL in declared, f"{SYMBOL} is not declared in include/vfa_hip.h"
-    assert hasattr(lib, SYMBOL), f"{SYMBOL} is not exported by the library"
-    args = re.search(r"\bint\s+" + SYMBOL + r"\s*\((.*?)\)\s*;", text, flags=re.S).group(1)
-    assert len(args.split(",")) == len(_lib.SIGNATURES[SYMBOL])
+def test_entry_point_is_declared_exported_and_bound():
+    """Declared, exported, bound, the same number of arguments: tests/test_abi.py, for every symbol.  Here: the cap is one number."""
+    from vfa_amd import eval_ops
+    text = open(os.path.join(REPO, "include", "vfa_hip.h")).read()
     cap = int(re.search(r"#define\s+VFA_CLEAR_MOD_MAX_SIDE\s+(\d+)", text).group(1))
     solver = open(os.path.join(REPO, "vfa_amd", "csrc", "vfa_assign.h")).read()
     assert cap == eval_ops.CLEAR_MOD_MAX_SIDE == int(re.search(r"kMaxSide\s*=\s*(\d+)", solver).group(1)) == 512
-    assert lib.vfa_abi_version() == 9 and _lib.ABI_VERSION == 9
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_solver_against_brute_force(harness, seed):
     """Every shape up to 7 x 7: optimal cost, a one-to-one table, no loop bound met; matrices with NaN / +inf return."""
-    out = _run(harness, "brute", str(seed), "3920")
+    out = run_harness(harness, "brute", str(seed), "3920")
     finite, odd = (int(v) for v in re.findall(r"(\d+) (?:finite|with)", out))
     assert finite + odd == 3920 and finite >= 2900 and odd >= 500
 
@@ -97,18 +77,18 @@ def test_solver_against_brute_force(harness, seed):
 def test_solver_against_scipy_records_of_the_fixture(harness, tmp_path):
     path = str(tmp_path / "frames.bin")
     n_frames = _frames_file(path)
-    out = _run(harness, "frames", path)
+    out = run_harness(harness, "frames", path)
     frames, stored, recomputed, compared = (int(v) for v in re.findall(r"\d+", out))
     assert frames == n_frames == 98 and stored >= 80 and recomputed >= 5 and compared >= 90
-    _run(harness, "wide", "1")  # frames of the cap's size
+    run_harness(harness, "wide", "1")  # frames of the cap's size
 
 
 def test_solver_under_the_host_sanitizers(sanitized_harness, tmp_path):
-    _run(sanitized_harness, "brute", "4", "3920")
+    run_harness(sanitized_harness, "brute", "4", "3920")
     path = str(tmp_path / "frames.bin")
     _frames_file(path)
-    _run(sanitized_harness, "frames", path)
-    _run(sanitized_harness, "wide", "2")
+    run_harness(sanitized_harness, "frames", path)
+    run_harness(sanitized_harness, "wide", "2")
 
 
 def test_clear_mod_host_only_branches():
@@ -147,26 +127,19 @@ def test_evaluate_detection_of_an_empty_result_file(tmp_path):
     assert eval_ops.evaluate_detection(str(res), str(gtf), "Wildtrack") == (0, 0, 0, 0)
 
 
-def _reference_shaped_checkout(root):
-    """A stand-in for the reference checkout behind compat/ (the technique of tests/test_ap_aos_cpu.py)."""
-    files = {
-        "vfa/__init__.py": "",
-        "vfa/evaluation/__init__.py": "",
-        "vfa/evaluation/evaluate.py": "from .pyeval.evaluateDetection import evaluateDetection_py\n",
-        "vfa/evaluation/pyeval/__init__.py": "",
-        "vfa/evaluation/pyeval/evaluateDetection.py": "ORIGIN = 'checkout'\n\n\ndef evaluateDetection_py(a, b, c):\n    return ORIGIN\n",
-        "vfa/evaluation/pyeval/CLEAR_MOD_HUN.py": "ORIGIN = 'checkout'\n",
-    }
-    for rel, text in files.items():
-        path = root / rel
-        path.parent.mkdir(parents=True, exist_ok=True)
-        path.write_text(text)
-    return str(root)
+CHECKOUT_FILES = {  # a stand-in for the reference checkout behind compat/ (native_common.write_checkout)
+    "vfa/__init__.py": "",
+    "vfa/evaluation/__init__.py": "",
+    "vfa/evaluation/evaluate.py": "from .pyeval.evaluateDetection import evaluateDetection_py\n",
+    "vfa/evaluation/pyeval/__init__.py": "",
+    "vfa/evaluation/pyeval/evaluateDetection.py": "ORIGIN = 'checkout'\n\n\ndef evaluateDetection_py(a, b, c):\n    return ORIGIN\n",
+    "vfa/evaluation/pyeval/CLEAR_MOD_HUN.py": "ORIGIN = 'checkout'\n",
+}
 
 
 @pytest.mark.parametrize("found_through", ["path", "VFA_REFERENCE_ROOT"])
 def test_alias_binds_the_metric_and_leaves_clear_mod_hun_to_the_checkout(tmp_path, found_through):
-    checkout = _reference_shaped_checkout(tmp_path / "checkout")
+    checkout = write_checkout(tmp_path / "checkout", CHECKOUT_FILES)
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(REPO, "compat"), REPO]))
     env.pop("VFA_REFERENCE_ROOT", None)
     if found_through == "path":

@@ -5,7 +5,6 @@ margins of those fixtures that make the comparison on the GPU unambiguous; the r
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,10 +12,9 @@ import torch
 
 from conftest import REPO
 import decode_common as dc
+from native_common import build_harness, run_harness
 
-SYMBOLS = ("vfa_bev_decode_f32", "vfa_bev_decode_workspace_bytes")
-HARNESS_SRC = os.path.join(REPO, "tests", "native", "decode_select_harness.cpp")
-GXX = ["g++", "-O1", "-std=c++17", "-Wall", "-ffp-contract=off"]
+GXX_FLAGS = ["-O1", "-std=c++17", "-Wall", "-ffp-contract=off"]
 
 
 @pytest.fixture(scope="module")
@@ -27,40 +25,21 @@ def built_lib():
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("decode_select") / "harness")
-    subprocess.check_call(GXX + ["-o", exe, HARNESS_SRC])
-    return exe
+    return build_harness(tmp_path_factory, "decode_select", "decode_select_harness.cpp", GXX_FLAGS)
 
 
 @pytest.fixture(scope="module")
 def sanitized_harness(tmp_path_factory):
-    """The same stand-alone program (its own ``main``, nothing preloaded) with the address and undefined-behaviour sanitizers."""
-    exe = str(tmp_path_factory.mktemp("decode_select_san") / "harness")
-    subprocess.check_call(GXX + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, HARNESS_SRC])
-    return exe
+    return build_harness(tmp_path_factory, "decode_select", "decode_select_harness.cpp", GXX_FLAGS, sanitized=True)
 
 
-def _run(exe, *args):
-    out = subprocess.run([exe, *args], capture_output=True, text=True, timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
-    return out.stdout
-
-
-def test_entry_points_are_declared_exported_and_bound(built_lib):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "vfa_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(?:int|size_t)\s+(vfa_\w+)\s*\(", text))
-    lib = ctypes.CDLL(built_lib)
-    from vfa_amd import _lib, eval_ops
-    for symbol in SYMBOLS:
-        assert symbol in declared, f"{symbol} is not declared in include/vfa_hip.h"
-        assert hasattr(lib, symbol), f"{symbol} is not exported by the library"
-        args = re.search(r"\b(?:int|size_t)\s+" + symbol + r"\s*\((.*?)\)\s*;", text, flags=re.S).group(1)
-        assert len(args.split(",")) == len(_lib.SIGNATURES[symbol])
+def test_entry_points_are_declared_exported_and_bound():
+    """Declared, exported, bound, the same number of arguments: tests/test_abi.py, for every symbol.  Here: the cap is one number."""
+    from vfa_amd import eval_ops
+    text = open(os.path.join(REPO, "include", "vfa_hip.h")).read()
     cap = int(re.search(r"#define\s+VFA_BEV_DECODE_MAX_TOPK\s+(\d+)", text).group(1))
     shared = open(os.path.join(REPO, "vfa_amd", "csrc", "vfa_decode.h")).read()
     assert cap == eval_ops.DECODE_MAX_TOPK == int(re.search(r"kMaxTopk\s*=\s*(\d+)", shared).group(1)) == 1024
-    assert lib.vfa_abi_version() == 9 and _lib.ABI_VERSION == 9          # the change only adds symbols
 
 
 def test_workspace_size_and_the_refusals_of_the_entry_point(built_lib):
@@ -92,18 +71,18 @@ def test_workspace_size_and_the_refusals_of_the_entry_point(built_lib):
 def test_selection_against_std_sort(harness, seed):
     """0 candidates, fewer than k, exactly k, all equal, ties across the k-th place, k = 1, k = 1024 of 1025, 70 000 cells, and 300
     random frames: the selected keys and their order are std::sort's."""
-    out = _run(harness, "cases", str(seed))
+    out = run_harness(harness, "cases", str(seed))
     passes, early, deep = (int(v) for v in re.findall(r"(\d+) (?:passes|selects|went)", out))
     assert passes > early > 100 and deep >= 20
 
 
 def test_key_packing(harness):
-    _run(harness, "keys")
+    run_harness(harness, "keys")
 
 
 def test_selection_under_the_host_sanitizers(sanitized_harness):
-    _run(sanitized_harness, "keys")
-    _run(sanitized_harness, "cases", "4")
+    run_harness(sanitized_harness, "keys")
+    run_harness(sanitized_harness, "cases", "4")
 
 
 @pytest.mark.parametrize("name", dc.FIXTURES)

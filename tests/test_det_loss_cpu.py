@@ -6,7 +6,6 @@ under the host sanitizers; the ABI of the new entry points and every refusal the
 import ctypes
 import os
 import re
-import subprocess
 from types import SimpleNamespace
 
 import numpy as np
@@ -15,10 +14,9 @@ import torch
 
 from conftest import REPO
 import loss_common as lc
+from native_common import build_harness, run_harness
 
-SYMBOLS = ("vfa_det_targets_f32", "vfa_det_loss_f32", "vfa_det_loss_backward_f32", "vfa_det_loss_workspace_bytes")
-HARNESS_SRC = os.path.join(REPO, "tests", "native", "loss_harness.cpp")
-GXX = ["g++", "-O1", "-std=c++17", "-Wall", "-ffp-contract=off"]
+GXX_FLAGS = ["-O1", "-std=c++17", "-Wall", "-ffp-contract=off"]
 BAD, UNSUPPORTED = 10001, 10002
 
 
@@ -30,23 +28,12 @@ def built_lib():
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("loss_rules") / "harness")
-    subprocess.check_call(GXX + ["-o", exe, HARNESS_SRC])
-    return exe
+    return build_harness(tmp_path_factory, "loss_rules", "loss_harness.cpp", GXX_FLAGS)
 
 
 @pytest.fixture(scope="module")
 def sanitized_harness(tmp_path_factory):
-    """The same stand-alone program (its own ``main``, nothing preloaded) with the address and undefined-behaviour sanitizers."""
-    exe = str(tmp_path_factory.mktemp("loss_rules_san") / "harness")
-    subprocess.check_call(GXX + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, HARNESS_SRC])
-    return exe
-
-
-def _run(exe, *args):
-    out = subprocess.run([exe, *args], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
-    return out.stdout
+    return build_harness(tmp_path_factory, "loss_rules", "loss_harness.cpp", GXX_FLAGS, sanitized=True)
 
 
 # ---- 1. the restatement against the reference's records ----------------------------------------------------------------------------
@@ -99,20 +86,20 @@ def test_fixture_margins(name):
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_rules_against_brute_force(harness, seed):
-    out = _run(harness, "cases", str(seed))
+    out = run_harness(harness, "cases", str(seed))
     live, dropped, overwritten = (int(v) for v in re.search(r"(\d+) live, (\d+) dropped, (\d+) overwritten", out).groups())
     assert live > 2000 and dropped > 2000 and overwritten > 1000 and "labels ok" in out
 
 
 def test_rules_under_the_host_sanitizers(sanitized_harness):
-    _run(sanitized_harness, "cases", "4")
+    run_harness(sanitized_harness, "cases", "4")
 
 
 def _harness_encode(exe, d):
     L, W = (int(v) for v in d["grid_lw"])
     from vfa_amd import _lib
     bits = np.stack([d["obj_location"][:, 0], d["obj_location"][:, 1], d["obj_rotation"]], axis=1).astype(np.float32).view(np.uint32)
-    out = _run(exe, "encode", str(L), str(W), str(_lib.CONV_KIND[str(d["base"])]), str(float(d["world_size"][0])),
+    out = run_harness(exe, "encode", str(L), str(W), str(_lib.CONV_KIND[str(d["base"])]), str(float(d["world_size"][0])),
                str(float(d["world_size"][1])), str(len(bits)), *[str(int(v)) for v in bits.ravel()])
     lines = out.strip().split("\n")
     rows = np.array([[int(v) for v in line.split()] for line in lines[1:]], dtype=np.int64).reshape(-1, 4)
@@ -136,21 +123,15 @@ def test_rules_against_the_fixtures(harness, sanitized_harness, name):
 
 # ---- 3. the library's plumbing ----------------------------------------------------------------------------------------------------
 
-def test_entry_points_are_declared_exported_and_bound(built_lib):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "vfa_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(?:int|size_t)\s+(vfa_\w+)\s*\(", text))
-    lib = ctypes.CDLL(built_lib)
-    from vfa_amd import _lib, loss
-    for symbol in SYMBOLS:
-        assert symbol in declared, f"{symbol} is not declared in include/vfa_hip.h"
-        assert hasattr(lib, symbol), f"{symbol} is not exported by the library"
-        args = re.search(r"\b(?:int|size_t)\s+" + symbol + r"\s*\((.*?)\)\s*;", text, flags=re.S).group(1)
-        assert len(args.split(",")) == len(_lib.SIGNATURES[symbol]), symbol
+def test_entry_points_are_declared_exported_and_bound():
+    """Declared, exported, bound, the same number of arguments: tests/test_abi.py, for every symbol.  Here: each cap is one number,
+    and the Makefile builds the file."""
+    from vfa_amd import loss
+    text = open(os.path.join(REPO, "include", "vfa_hip.h")).read()
     shared = open(os.path.join(REPO, "vfa_amd", "csrc", "vfa_loss.h")).read()
     for macro, constant in (("VFA_DET_MAX_OBJECTS", "kMaxObjects"), ("VFA_DET_MAX_ROT", "kMaxRot")):
         cap = int(re.search(r"#define\s+" + macro + r"\s+(\d+)", text).group(1))
         assert cap == int(re.search(constant + r"\s*=\s*(\d+)", shared).group(1)) == loss.MAX_OBJECTS == 1024
-    assert lib.vfa_abi_version() == 9 and _lib.ABI_VERSION == 9          # the change only adds symbols
     makefile = open(os.path.join(REPO, "vfa_amd", "csrc", "Makefile")).read()
     assert "vfa_loss.hip" in makefile and "vfa_loss.h" in makefile.split("HDRS")[1]
 

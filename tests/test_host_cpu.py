@@ -14,6 +14,7 @@ import torch.multiprocessing as mp
 import torch.nn as nn
 
 from conftest import REPO
+from native_common import write_checkout
 
 
 def _args():
@@ -44,24 +45,18 @@ def test_vfanet_builds_with_the_reference_default_arguments(tmp_path, monkeypatc
     assert not torch.all(net2.base.layer2[0].conv1.weight == 0.5)
 
 
-def _reference_shaped_checkout(root):
-    """A stand-in for the reference checkout behind compat/: the package layout the alias package extends (vfa/model/loss.py,
-    vfa/evaluation/pyeval/IoU.py -> cuda_op/cuda_ext.py -> ``import sort_vertices``), each module a line or two written here."""
-    files = {
-        "vfa/__init__.py": "",
-        "vfa/model/__init__.py": "",
-        "vfa/model/loss.py": "ORIGIN = 'checkout'\n",
-        "vfa/evaluation/__init__.py": "",
-        "vfa/evaluation/pyeval/__init__.py": "",
-        "vfa/evaluation/pyeval/cuda_op/__init__.py": "",
-        "vfa/evaluation/pyeval/cuda_op/cuda_ext.py": "import sort_vertices\n\nbound = sort_vertices.sort_vertices_forward\n",
-        "vfa/evaluation/pyeval/IoU.py": "from .cuda_op.cuda_ext import bound\n",
-    }
-    for rel, text in files.items():
-        path = root / rel
-        path.parent.mkdir(parents=True, exist_ok=True)
-        path.write_text(text)
-    return str(root)
+# A stand-in for the reference checkout behind compat/ (native_common.write_checkout): the package layout the alias package extends
+# (vfa/model/loss.py, vfa/evaluation/pyeval/IoU.py -> cuda_op/cuda_ext.py -> ``import sort_vertices``)
+CHECKOUT_FILES = {
+    "vfa/__init__.py": "",
+    "vfa/model/__init__.py": "",
+    "vfa/model/loss.py": "ORIGIN = 'checkout'\n",
+    "vfa/evaluation/__init__.py": "",
+    "vfa/evaluation/pyeval/__init__.py": "",
+    "vfa/evaluation/pyeval/cuda_op/__init__.py": "",
+    "vfa/evaluation/pyeval/cuda_op/cuda_ext.py": "import sort_vertices\n\nbound = sort_vertices.sort_vertices_forward\n",
+    "vfa/evaluation/pyeval/IoU.py": "from .cuda_op.cuda_ext import bound\n",
+}
 
 
 def test_reference_named_alias_package_resolves_to_the_build(tmp_path):
@@ -74,7 +69,7 @@ def test_reference_named_alias_package_resolves_to_the_build(tmp_path):
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd="/")
     assert out.returncode == 0 and out.stdout.strip() == "ok", out.stderr
     # with a checkout of the reference's layout behind it on the path, the REST of vfa.* resolves to that checkout
-    checkout = _reference_shaped_checkout(tmp_path / "checkout")
+    checkout = write_checkout(tmp_path / "checkout", CHECKOUT_FILES)
     env["PYTHONPATH"] += os.pathsep + checkout
     code = (f"import vfa.model.loss as l, vfa.model.vfa_op as a, vfa_amd, os; checkout = {checkout!r};"
             "assert l.__file__.startswith(checkout) and l.ORIGIN == 'checkout' and a.VFA is vfa_amd.VFA; print('ok')")

@@ -108,6 +108,35 @@ def _frames_call(det, det_begin, gt, gt_begin, n_frames, pair_begin, n_pairs, wa
     return iou, best_idx, best_iou
 
 
+def _frame_tables(who, det_frame, gt_frame, n_det, n_gt, n_frames, with_matrix, row="box"):
+    """The offset tables ``match_frames`` and ``match_frames_hungarian`` (``who``) hand to their kernels, from the sorted frame
+    counters -> ``(n_frames, det_begin, gt_begin, pair_begin, n_pairs)``: the begins int32, ``n_frames + 1`` long; ``pair_begin``
+    int64 (``None`` and 0 pairs without a matrix).  Plain torch on the device the counters live on.  The host waits are the two the
+    callers document: ``n_frames is None`` reads the largest counter (and the order), ``with_matrix`` the number of pairs."""
+    det_frame, gt_frame = det_frame.to(torch.int64).contiguous(), gt_frame.to(torch.int64).contiguous()
+    if det_frame.shape != (n_det,) or gt_frame.shape != (n_gt,):
+        raise ValueError(f"one frame counter per {row} is needed")
+    dev = det_frame.device
+    if n_frames is None:
+        both = torch.cat([det_frame, gt_frame])
+        if both.numel() == 0:
+            n_frames = 0
+        else:
+            ordered = torch.stack([(det_frame[1:] >= det_frame[:-1]).all(), (gt_frame[1:] >= gt_frame[:-1]).all(), both.min() >= 0])
+            hi, ok = int(both.max()), bool(ordered.all())
+            if not ok:
+                raise ValueError(f"{who}: frame counters must be non-negative and sorted (non-decreasing)")
+            n_frames = hi + 1
+    edges = torch.arange(n_frames + 1, dtype=torch.int64, device=dev)
+    det_begin64, gt_begin64 = torch.searchsorted(det_frame, edges), torch.searchsorted(gt_frame, edges)
+    det_begin, gt_begin = det_begin64.to(torch.int32), gt_begin64.to(torch.int32)
+    if not with_matrix:
+        return n_frames, det_begin, gt_begin, None, 0
+    pair_begin = torch.zeros(n_frames + 1, dtype=torch.int64, device=dev)
+    pair_begin[1:] = torch.cumsum((det_begin64[1:] - det_begin64[:-1]) * (gt_begin64[1:] - gt_begin64[:-1]), 0)
+    return n_frames, det_begin, gt_begin, pair_begin, int(pair_begin[-1])
+
+
 def _box_rows(t, name):
     if t.dim() != 2 or t.shape[1] != 7:
         raise ValueError(f"{name} must be (n, 7) boxes x y z l w h alpha, got {tuple(t.shape)}")
@@ -140,30 +169,10 @@ def match_frames(det, det_frame, gt, gt_frame, n_frames=None, with_matrix=False)
     ``(P_f, G_f)`` matrix is ``iou[pair_begin[f]:pair_begin[f + 1]]``, detection-major (one more synchronisation, for its size)."""
     _lib.require_device(det, det_frame, gt, gt_frame)
     det, gt = _box_rows(det, "det"), _box_rows(gt, "gt")
-    det_frame, gt_frame = det_frame.to(torch.int64).contiguous(), gt_frame.to(torch.int64).contiguous()
-    if det_frame.shape != (det.shape[0],) or gt_frame.shape != (gt.shape[0],):
-        raise ValueError("one frame counter per box is needed")
-    dev = det.device
-    if n_frames is None:
-        both = torch.cat([det_frame, gt_frame])
-        if both.numel() == 0:
-            n_frames = 0
-        else:
-            ordered = torch.stack([(det_frame[1:] >= det_frame[:-1]).all(), (gt_frame[1:] >= gt_frame[:-1]).all(), both.min() >= 0])
-            hi, ok = int(both.max()), bool(ordered.all())
-            if not ok:
-                raise ValueError("match_frames: frame counters must be non-negative and sorted (non-decreasing)")
-            n_frames = hi + 1
-    edges = torch.arange(n_frames + 1, dtype=torch.int64, device=dev)
-    det_begin64, gt_begin64 = torch.searchsorted(det_frame, edges), torch.searchsorted(gt_frame, edges)
-    det_begin, gt_begin = det_begin64.to(torch.int32), gt_begin64.to(torch.int32)
-    if not with_matrix:
-        _, best_idx, best_iou = _frames_call(det, det_begin, gt, gt_begin, n_frames, None, 0, False, True)
-        return best_idx, best_iou
-    pair_begin = torch.zeros(n_frames + 1, dtype=torch.int64, device=dev)
-    pair_begin[1:] = torch.cumsum((det_begin64[1:] - det_begin64[:-1]) * (gt_begin64[1:] - gt_begin64[:-1]), 0)
-    iou, best_idx, best_iou = _frames_call(det, det_begin, gt, gt_begin, n_frames, pair_begin, int(pair_begin[-1]), True, True)
-    return best_idx, best_iou, iou, pair_begin
+    n_frames, det_begin, gt_begin, pair_begin, n_pairs = _frame_tables("match_frames", det_frame, gt_frame, det.shape[0], gt.shape[0],
+                                                                       n_frames, with_matrix)
+    iou, best_idx, best_iou = _frames_call(det, det_begin, gt, gt_begin, n_frames, pair_begin, n_pairs, with_matrix, True)
+    return (best_idx, best_iou, iou, pair_begin) if with_matrix else (best_idx, best_iou)
 
 
 def ap_aos_from_matches(conf, matched, delta_rot, n_gt):
@@ -209,6 +218,25 @@ def _table(a, width, name):
     return a
 
 
+def _evaluation_set(gt, det):
+    """The reference's bookkeeping of an evaluation set, for both metrics: ``gt`` and ``det`` rows whose column 0 is the frame
+    number, ``det`` not empty -> ``(frames, det, det_ctr, gt, gt_ctr, n_frames)``, the rows kept and stably sorted by their frame
+    counter ``0 .. n_frames - 1``, ``frames[counter]`` the frame number."""
+    frames = np.unique(det[:, 0])               # the frames are those that HAVE detections (evaluateAPAOS.py:111, :123;
+    det_ctr = np.searchsorted(frames, det[:, 0])                                          # evaluateDetection.py:30, :41-42)
+    det = det[np.argsort(det_ctr, kind="stable")]
+    det_ctr = np.sort(det_ctr)
+    gt = gt[np.isin(gt[:, 0], frames)]          # ... so the ground truth of other frames does not count
+    if gt.shape[0] == 0:                        # (the reference fails there on ``max`` of an empty array)
+        raise ValueError("no ground truth in the frames that have detections")
+    gt_ctr = np.searchsorted(frames, gt[:, 0])
+    gt = gt[np.argsort(gt_ctr, kind="stable")]
+    gt_ctr = np.sort(gt_ctr)
+    n_frames = int(gt_ctr.max()) + 1            # the counters run to the last frame that has ground truth (evaluateAPAOS.py:10-12,
+    det, det_ctr = det[det_ctr < n_frames], det_ctr[det_ctr < n_frames]     # CLEAR_MOD_HUN.py:29): later detections are dropped
+    return frames, det, det_ctr, gt, gt_ctr, n_frames
+
+
 def ap_aos(gt, det, thresholds=(0.75, 0.5, 0.25), device="cuda"):
     """AP and AOS of a detection set at each IoU threshold -> ``[(AP, AOS), ...]`` as fractions, one launch for all the IoUs.
 
@@ -226,18 +254,7 @@ def ap_aos(gt, det, thresholds=(0.75, 0.5, 0.25), device="cuda"):
     gt, det = _table(gt, 8, "gt"), _table(det, 9, "det")
     if det.shape[0] == 0:
         raise ValueError("detection is empty")
-    frames = np.unique(det[:, 0])
-    det_ctr = np.searchsorted(frames, det[:, 0])
-    det = det[np.argsort(det_ctr, kind="stable")]
-    det_ctr = np.sort(det_ctr)
-    gt = gt[np.isin(gt[:, 0], frames)]
-    if gt.shape[0] == 0:
-        raise ValueError("no ground truth in the frames that have detections")
-    gt_ctr = np.searchsorted(frames, gt[:, 0])
-    gt = gt[np.argsort(gt_ctr, kind="stable")]
-    gt_ctr = np.sort(gt_ctr)
-    n_frames = int(gt_ctr.max()) + 1
-    det, det_ctr = det[det_ctr < n_frames], det_ctr[det_ctr < n_frames]
+    _, det, det_ctr, gt, gt_ctr, n_frames = _evaluation_set(gt, det)
     dev = torch.device(device)
     best_idx, best_iou = match_frames(torch.from_numpy(det[:, 1:8]).to(dev), torch.from_numpy(det_ctr).to(dev),
                                       torch.from_numpy(gt[:, 1:8]).to(dev), torch.from_numpy(gt_ctr).to(dev), n_frames=n_frames)
@@ -293,36 +310,15 @@ def match_frames_hungarian(det_xy, det_frame, gt_xy, gt_frame, n_frames=None, td
     ground-truth-major like the reference's ``dist[o, e]`` (one more synchronisation, for its size)."""
     _lib.require_device(det_xy, det_frame, gt_xy, gt_frame)
     det_xy, gt_xy = _xy_rows(det_xy, "det_xy"), _xy_rows(gt_xy, "gt_xy")
-    det_frame, gt_frame = det_frame.to(torch.int64).contiguous(), gt_frame.to(torch.int64).contiguous()
-    if det_frame.shape != (det_xy.shape[0],) or gt_frame.shape != (gt_xy.shape[0],):
-        raise ValueError("one frame counter per position is needed")
-    dev = det_xy.device
-    if n_frames is None:
-        both = torch.cat([det_frame, gt_frame])
-        if both.numel() == 0:
-            n_frames = 0
-        else:
-            ordered = torch.stack([(det_frame[1:] >= det_frame[:-1]).all(), (gt_frame[1:] >= gt_frame[:-1]).all(), both.min() >= 0])
-            hi, ok = int(both.max()), bool(ordered.all())
-            if not ok:
-                raise ValueError("match_frames_hungarian: frame counters must be non-negative and sorted (non-decreasing)")
-            n_frames = hi + 1
-    edges = torch.arange(n_frames + 1, dtype=torch.int64, device=dev)
-    det_begin64, gt_begin64 = torch.searchsorted(det_frame, edges), torch.searchsorted(gt_frame, edges)
-    det_begin, gt_begin = det_begin64.to(torch.int32), gt_begin64.to(torch.int32)
-    G = gt_xy.shape[0]
+    n_frames, det_begin, gt_begin, pair_begin, n_pairs = _frame_tables("match_frames_hungarian", det_frame, gt_frame, det_xy.shape[0],
+                                                                       gt_xy.shape[0], n_frames, with_matrix, row="position")
+    dev, G = det_xy.device, gt_xy.shape[0]
     gt_match = torch.full((G,), -1, dtype=torch.int32, device=dev)
     gt_dist = torch.full((G,), float("inf"), dtype=torch.float64, device=dev)
     frame_counts = torch.zeros((n_frames, 4), dtype=torch.int64, device=dev)
     frame_cost = torch.zeros(n_frames, dtype=torch.float64, device=dev)
     frame_status = torch.zeros(n_frames, dtype=torch.int32, device=dev)
-    dist = pair_begin = None
-    n_pairs = 0
-    if with_matrix:
-        pair_begin = torch.zeros(n_frames + 1, dtype=torch.int64, device=dev)
-        pair_begin[1:] = torch.cumsum((det_begin64[1:] - det_begin64[:-1]) * (gt_begin64[1:] - gt_begin64[:-1]), 0)
-        n_pairs = int(pair_begin[-1])
-        dist = torch.full((n_pairs,), float("nan"), dtype=torch.float64, device=dev)
+    dist = torch.full((n_pairs,), float("nan"), dtype=torch.float64, device=dev) if with_matrix else None
     _lib.call("vfa_clear_mod_frames_f64", _lib.ptr(det_xy), _lib.ptr(det_begin), _lib.ptr(gt_xy), _lib.ptr(gt_begin), n_frames,
               det_xy.shape[0], G, float(td), _lib.ptr(pair_begin), n_pairs, _lib.ptr(dist), _lib.ptr(gt_match), _lib.ptr(gt_dist),
               _lib.ptr(frame_counts), _lib.ptr(frame_cost), _lib.ptr(frame_status), _lib.current_stream_handle())
@@ -338,18 +334,7 @@ def clear_mod_totals(gt, det, td=30.0, device="cuda"):
         raise ValueError("detection is empty")
     if not (np.isfinite(gt).all() and np.isfinite(det).all()):
         raise ValueError("clear_mod: frame numbers and coordinates must be finite")
-    frames = np.unique(det[:, 0])
-    det_ctr = np.searchsorted(frames, det[:, 0])
-    det = det[np.argsort(det_ctr, kind="stable")]
-    det_ctr = np.sort(det_ctr)
-    gt = gt[np.isin(gt[:, 0], frames)]
-    if gt.shape[0] == 0:
-        raise ValueError("no ground truth in the frames that have detections")
-    gt_ctr = np.searchsorted(frames, gt[:, 0])
-    gt = gt[np.argsort(gt_ctr, kind="stable")]
-    gt_ctr = np.sort(gt_ctr)
-    n_frames = int(gt_ctr.max()) + 1
-    det, det_ctr = det[det_ctr < n_frames], det_ctr[det_ctr < n_frames]
+    frames, det, det_ctr, gt, gt_ctr, n_frames = _evaluation_set(gt, det)
     sizes = np.maximum(np.bincount(det_ctr, minlength=n_frames), np.bincount(gt_ctr, minlength=n_frames))
     if sizes.max() > CLEAR_MOD_MAX_SIDE:
         worst = int(np.argmax(sizes))
@@ -443,15 +428,14 @@ class BEVDecoder:
         self.grid_size = self.world_size / np.array(cube_LWH)[:2]
         self.dimension_mean = dimension_mean
 
-    _conf = None  # (decode_frames: this frame's slice of the batched NMS)
-
     def nms(self, heatmap):
-        return bev_nms(heatmap) if self._conf is None else self._conf
+        return bev_nms(heatmap)
 
-    def _peaks(self, pred):
+    def _peaks(self, pred, conf=None):
+        """``conf``: the NMS of the heatmap where the caller has it already (``decode_frames``); ``None``: ``self.nms(heatmap)``."""
         heatmap, tytx = pred["heatmap"], pred["loc_offset"]
         device, dtype = heatmap.device, heatmap.dtype
-        conf = self.nms(heatmap).flatten(start_dim=2).transpose(1, 2)            # (1, L*W, 1)
+        conf = (self.nms(heatmap) if conf is None else conf).flatten(start_dim=2).transpose(1, 2)     # (1, L*W, 1)
         conf, _ = torch.max(conf, dim=-1)
         L, W = heatmap.shape[2:]
         grid_y, grid_x = torch.meshgrid(torch.arange(L, dtype=dtype, device=device), torch.arange(W, dtype=dtype, device=device),
@@ -462,8 +446,8 @@ class BEVDecoder:
         _, topk_index = torch.topk(conf, k=min(self.topk, conf.shape[1]), dim=1)
         return conf, cy, cx, topk_index
 
-    def decode3d(self, pred, cls_thresh):
-        conf, cy, cx, topk_index = self._peaks(pred)
+    def decode3d(self, pred, cls_thresh, *, conf=None):
+        conf, cy, cx, topk_index = self._peaks(pred, conf)
         thtwtl, orient = pred["dim_offset"], pred["rotation"]
         mean = self.dimension_mean
         dims = [torch.exp(thtwtl[..., k]).flatten(start_dim=1) * mean[k] for k in range(3)]
@@ -476,31 +460,24 @@ class BEVDecoder:
                 "dimension": torch.stack([out[3][mask], out[4][mask], out[5][mask]], dim=-1),
                 "rotation": torch.deg2rad(out[6][mask].to(torch.float32))}
 
-    def decode2d(self, pred, cls_thresh):
-        conf, cy, cx, topk_index = self._peaks(pred)
+    def decode2d(self, pred, cls_thresh, *, conf=None):
+        conf, cy, cx, topk_index = self._peaks(pred, conf)
         out = [torch.gather(x, dim=1, index=topk_index) for x in [conf, cy, cx]]
         mask = out[0] > cls_thresh
         first, second = (out[1], out[2]) if self.base == "Wildtrack" else (out[2], out[1])
         return {"conf": out[0][mask],
                 "location": torch.stack([first[mask], second[mask], torch.zeros_like(out[1][mask])], dim=-1)}
 
-    def batch_decode(self, pred, cls_thresh):
-        return self.decode3d(pred, cls_thresh) if self.base in ("MultiviewC", "MVM3D") else self.decode2d(pred, cls_thresh)
+    def batch_decode(self, pred, cls_thresh, *, conf=None):
+        decode = self.decode3d if self.base in ("MultiviewC", "MVM3D") else self.decode2d
+        return decode(pred, cls_thresh, conf=conf)
 
     def decode_frames(self, pred, cls_thresh):
         """A batch of B frames (every head (B, ...)) -> a list of B per-frame results, each what ``batch_decode`` gives for that
         frame alone; the NMS of all frames runs as one launch (``bev_nms_batch``)."""
         B = pred["heatmap"].shape[0]
         conf = bev_nms_batch(pred["heatmap"])
-        out = []
-        for b in range(B):
-            one = {k: v[b:b + 1] for k, v in pred.items()}
-            self._conf = conf[b:b + 1]
-            try:
-                out.append(self.batch_decode(one, cls_thresh))
-            finally:
-                self._conf = None
-        return out
+        return [self.batch_decode({k: v[b:b + 1] for k, v in pred.items()}, cls_thresh, conf=conf[b:b + 1]) for b in range(B)]
 
     def decode_fused(self, pred, cls_thresh):
         """A batch of B >= 1 frames (every head ``(B, ...)``) -> detections in tensors of a FIXED shape, in one library call
