@@ -828,6 +828,37 @@ int vfa_det_loss_backward_f32(const float *coef, const float *heatmap, const lon
                               const float *table, const int *counts, int B, int L, int W, int k, int R, float *d_heatmap,
                               float *d_loc_offset, float *d_dim_offset, float *d_rotation_at, void *stream);
 
+/* ---- the dense heat-map target of a training step rendered from the object tensors, no host round trip --------------------------
+ *                                       replaces vfa/data/GK.py (RotationGaussianKernel, GaussianKernel) and the cached .npy maps
+ * Both take what vfa_det_targets_f32 takes -- location (B, K, loc_width), count (B) int32 clamped to [0, K], world, kind -- and give
+ * every object the cell that call gives it (csrc/vfa_loss.h; outside the map or non-finite: dropped), so the cells of heat equal
+ * to 1 are the cells vfa_det_targets_f32 lists.  heat (B, L, W) contiguous, every element written.  Slots behind count are not read.
+ * The rules: csrc/vfa_heat.h.
+ *
+ * vfa_heat_rgk_f32: per object a rotated Gaussian kernel of n = k + 1 <= VFA_HEAT_MAX_KERNEL taps per side, k = (int)(ceil(max(w, l)
+ *   * alpha) * ratio), from dimension (B, K, 3) = (h, w, l) and angle_deg (B, K) FLOAT64 degrees (the annotation's number); taps in
+ *   float32, rotation and blend in float64 with the reference's operation order, pasted with its arg-max on the object's cell by an
+ *   integer max on the bit patterns, the centre 1: the map does not depend on the order of the objects, the same bits on every run
+ *   and in any batch.  DEVIATIONS: an arg-max tie takes the first cell in row-major order (the reference raises); kernel cells
+ *   outside the map are dropped (the reference raises); an object with k > 64 (or k < 2, a non-positive or non-finite dimension or
+ *   angle) contributes its centre only and is counted in n_clipped (B) int32.  One workgroup per (object slot, frame).
+ * vfa_heat_gk_f32: occupancy (a duplicate counts once) convolved with table ((2r+1)^2 float32 on the DEVICE, r <=
+ *   VFA_HEAT_MAX_RADIUS), zero padding, float64 sum in raster order rounded once, occupied cells 1 (no clip above 1).
+ *   workspace: vfa_heat_workspace_bytes(B, L, W) bytes (one occupancy byte per cell), the caller's.
+ *
+ * Errors, decided before anything is launched, with the codes and limits of the vfa_det_* family: a negative size, a NULL required
+ * pointer, a short workspace, loc_width outside {2, 3}, world <= 0, kind outside 0..2, alpha <= 0, ratio outside 1..1024, r < 0:
+ * VFA_ERR_BAD_ARGUMENT; K > VFA_DET_MAX_OBJECTS, r > VFA_HEAT_MAX_RADIUS, B > 65535, L * W >= 2^31 - 1024: VFA_ERR_UNSUPPORTED;
+ * B == 0 or L * W == 0 returns 0 and launches nothing. */
+#define VFA_HEAT_MAX_KERNEL 65
+#define VFA_HEAT_MAX_RADIUS 16
+size_t vfa_heat_workspace_bytes(int B, int L, int W);
+int vfa_heat_rgk_f32(const float *location, int loc_width, const int *count, const float *dimension, const double *angle_deg, int B,
+                     int K, int L, int W, float world0, float world1, int kind, double alpha, int ratio, float *heat, int *n_clipped,
+                     void *stream);
+int vfa_heat_gk_f32(const float *location, int loc_width, const int *count, const float *table, int r, int B, int K, int L, int W,
+                    float world0, float world1, int kind, void *workspace, size_t workspace_bytes, float *heat, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,11 @@ SIGNATURES = {
     "vfa_det_loss_workspace_bytes": [_c_int, _c_int, _c_int],
     "vfa_det_loss_f32": [_vp] * 17 + [_c_int] * 5 + [_vp, _c_size_t, _vp, _vp, _vp, _vp],
     "vfa_det_loss_backward_f32": [_vp] * 18 + [_c_int] * 5 + [_vp, _vp, _vp, _vp, _vp],
+    "vfa_heat_workspace_bytes": [_c_int, _c_int, _c_int],
+    "vfa_heat_rgk_f32": [_vp, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_int, _c_double, _c_int, _vp,
+                         _vp, _vp],
+    "vfa_heat_gk_f32": [_vp, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_int, _vp, _c_size_t, _vp,
+                        _vp],
 }
 
 _lib = None

@@ -4,10 +4,14 @@
 
     objs = pack_objects(frames, device)                                       # the only place that touches Python objects
     targets = encoder.encode(objs.location, objs.count, objs.dimension, objs.rotation, grid_lw=(L, W))
+    gt_heatmap = encoder.heatmap(objs.location, objs.count, objs.dimension, rotation_deg=degrees, heatmap_type="RGK", grid_lw=(L, W))
     pred = model(images, calibs, grid, rotation_at=targets.cells)
     detection_loss(pred, targets, gt_heatmap)["loss"].sum().backward()
 
-Everything between the object tensors and ``backward()`` is stream-ordered HIP (``vfa_amd/csrc/vfa_loss.hip``): no ``.item()``, no
+``gt_heatmap`` is rendered on the device from the same object tensors (``TargetEncoder.heatmap``: the reference's ``vfa/data/GK.py``
+maps, which its datasets precompute on the host and cache): its cells equal to 1 are ``targets.cells``, and the object lists are
+the only input of the step.  Everything between the object tensors and ``backward()`` is stream-ordered HIP
+(``vfa_amd/csrc/vfa_loss.hip``, ``vfa_heat.hip``): no ``.item()``, no
 ``int(tensor)``, outputs of fixed shape, so the step can be captured in a graph.  Deviations from the reference, all in cases where it
 has no defined value: an object outside the map (or with a non-finite coordinate) is dropped instead of raising / wrapping a negative
 index; an angle label outside ``-R/2 .. 3R/2 - 1`` wraps modulo ``R``; a frame without positives has 0 for the three sparse terms
@@ -33,6 +37,16 @@ def label_table(angle_range=360, angle_radius=6):
         raise ValueError(f"angle_range must be even and in 2 .. 1024, got {angle_range}")
     x = np.arange(-(R // 2), R // 2, dtype=np.float64)
     return torch.from_numpy(np.exp(-x ** 2 / (2.0 * float(angle_radius) ** 2)).astype(np.float32))
+
+
+def gk_table(grid_reduce=4, radius=8):
+    """``table[y][x] = exp(-(x^2 + y^2) / (2 sigma^2))``, ``sigma^2 = 8 / grid_reduce``, in float64, rounded to float32: the
+    ``(2 radius + 1)^2`` kernel of the reference's ``GaussianKernel`` (``multivariate_normal.pdf / max``)."""
+    r = int(radius)
+    if not 0 <= r <= 16 or not float(grid_reduce) > 0:
+        raise ValueError(f"gk_table: radius in 0 .. 16 and grid_reduce > 0, got {radius}, {grid_reduce}")
+    x = np.arange(-r, r + 1, dtype=np.float64)
+    return torch.from_numpy(np.exp(-(x[None, :] ** 2 + x[:, None] ** 2) / (2.0 * (8.0 / float(grid_reduce)))).astype(np.float32))
 
 
 class PackedObjects(NamedTuple):
@@ -134,6 +148,7 @@ class TargetEncoder:
         self.angle_range, self.angle_radius, self.max_objects = int(angle_range), angle_radius, int(max_objects)
         self._table_host = label_table(angle_range, angle_radius)
         self._tables = {}
+        self._gk_tables = {}
 
     def table(self, device):
         """The label table on ``device`` (uploaded once per device, outside any captured region)."""
@@ -153,6 +168,46 @@ class TargetEncoder:
         cells, n_pos, loc_offset, dim_offset, label = ops.det_targets(location, count, dimension, rotation, self.dimension_mean,
                                                                       self.world_size, (L, W), self.kind)
         return DetTargets(cells, n_pos, loc_offset, dim_offset, label, self.table(location.device) if three_d else None)
+
+
+    def gk_table(self, device, grid_reduce=4, radius=8):
+        """The GK table ``float32(exp(-(x^2 + y^2) / (2 sigma^2)))``, ``sigma^2 = 8 / grid_reduce``, ``(2 radius + 1)^2``, on
+        ``device``: made once in float64 numpy and uploaded once per device, outside any captured region (what the reference's
+        ``multivariate_normal.pdf / max`` gives, in every float32 bit)."""
+        key = (str(device), float(grid_reduce), int(radius))
+        if key not in self._gk_tables:
+            self._gk_tables[key] = gk_table(grid_reduce, radius).to(device)
+        return self._gk_tables[key]
+
+    def heatmap(self, location, count, dimension=None, rotation=None, rotation_deg=None, heatmap_type="RGK", grid_lw=None, alpha=0.01,
+                ratio=8, grid_reduce=4, radius=8, return_clipped=False):
+        """The dense heat-map target ``(B, L, W)`` float32 of ``detection_loss`` from the tensors ``encode`` takes, rendered on the
+        device (``vfa_heat_rgk_f32`` / ``vfa_heat_gk_f32``, rules in ``vfa_amd/csrc/vfa_heat.h``); its cells equal to 1 are
+        ``encode(...).cells``.
+
+        ``"RGK"`` (the reference's ``RotationGaussianKernel``) needs ``dimension (B, K, 3)`` = (h, w, l) and the angle:
+        ``rotation_deg (B, K)``, float32 or float64, the ANNOTATION's degrees -- the reference renders from that number, so this
+        is the path that reproduces its maps -- or else ``rotation (B, K)`` in radians, converted on the device with
+        ``torch.rad2deg(rotation.double())``: not the annotation's bits (the radians were rounded to float32), the same map up to
+        the rounding of the angle.  ``alpha`` / ``ratio`` as in the reference; an object whose kernel would have more than 65 taps
+        per side gives its centre only (``return_clipped=True`` also returns their number per frame, ``(B,)`` int32).
+        ``"GK"`` (``GaussianKernel``) needs neither: ``radius`` and ``sigma^2 = 8 / grid_reduce`` of its table.
+        Deviations, where the reference has no value: an arg-max tie of a rotated kernel takes the first cell, kernel cells outside
+        the map are dropped, an object outside the map is dropped, two objects in a cell count once."""
+        L, W = (int(round(v)) for v in self.grid_size) if grid_lw is None else grid_lw
+        _lib.require_device(location, count, dimension, rotation, rotation_deg)
+        if heatmap_type == "GK":
+            heat = ops.heat_gk(location, count, self.gk_table(location.device, grid_reduce, radius), self.world_size, (L, W), self.kind)
+            return (heat, torch.zeros_like(count)) if return_clipped else heat
+        if heatmap_type != "RGK":
+            raise ValueError(f"TargetEncoder.heatmap: heatmap_type must be 'RGK' or 'GK', got {heatmap_type!r}")
+        if dimension is None or (rotation is None and rotation_deg is None):
+            raise ValueError("TargetEncoder.heatmap: 'RGK' needs dimension and rotation_deg (degrees) or rotation (radians)")
+        if rotation_deg is not None and rotation_deg.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"TargetEncoder.heatmap: rotation_deg must be float32 or float64, got {rotation_deg.dtype}")
+        degrees = rotation_deg.double() if rotation_deg is not None else torch.rad2deg(rotation.double())
+        heat, clipped = ops.heat_rgk(location, count, dimension, degrees, self.world_size, (L, W), self.kind, alpha, ratio)
+        return (heat, clipped) if return_clipped else heat
 
 
 class _DetLoss(torch.autograd.Function):
@@ -177,7 +232,8 @@ class _DetLoss(torch.autograd.Function):
 
 def detection_loss(pred, targets, gt_heatmap, loss_weight=(1.0, 1.0, 1.0, 1.0)):
     """The reference's loss (``loss.py:45-102``) per frame of a batch: ``pred`` is what ``VFANet`` returns (3D if it has
-    ``dim_offset``), ``targets`` a ``DetTargets``, ``gt_heatmap (B, L, W)`` or ``(B, 1, L, W)`` the dense heat-map target.  Returns
+    ``dim_offset``), ``targets`` a ``DetTargets``, ``gt_heatmap (B, L, W)`` or ``(B, 1, L, W)`` the dense heat-map target: what
+    ``TargetEncoder.heatmap`` renders from the same object tensors (or a map the dataset precomputed).  Returns
     ``{"loss", "loss_heatmap", "loss_pos"[, "loss_hwl", "loss_ang"]}``, device tensors of shape ``(B,)``, weighted like the
     reference's ``loss_dict``; differentiable with respect to the heads.  ``pred["rotation_at"]`` must have been evaluated at
     ``targets.cells`` (``pred["rotation_cells"]``, the same tensor); a dense ``pred["rotation"]`` is gathered at those cells."""

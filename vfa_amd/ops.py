@@ -1269,3 +1269,51 @@ def det_loss_backward(coef, counts, heatmap, gt_heatmap, loc, dim, rot, cells, n
     _launch("vfa_det_loss_backward_f32", _lib.ptr(coef.contiguous()), *ptrs, _lib.ptr(counts.contiguous()), B, L, W, k, R, _lib.ptr(d_heat),
             _lib.ptr(d_loc), _lib.ptr(d_dim), _lib.ptr(d_rot), _lib.current_stream_handle(), tag=(B, L, W, k, R))
     return d_heat, d_loc, d_dim, d_rot
+
+
+def _heat_operands(name, location, count):
+    _det_f32(name, location=location)
+    _lib.require_device(count)
+    if location.dim() != 3 or location.shape[2] not in (2, 3) or count.dtype != torch.int32 or count.shape != location.shape[:1]:
+        raise ValueError(f"{name}: location (B, K, 2|3) and count (B) int32, got {tuple(location.shape)}, {count.dtype} {tuple(count.shape)}")
+    return location.contiguous(), count.contiguous()
+
+
+def heat_rgk(location, count, dimension, angle_deg, world_size=(1.0, 1.0), grid_lw=(1, 1), kind=0, alpha=0.01, ratio=8):
+    """``vfa_heat_rgk_f32``: location (B, K, 2|3), count (B) int32, dimension (B, K, 3) = (h, w, l), angle_deg (B, K) FLOAT64 degrees
+    -> (heat (B, L, W) float32, n_clipped (B) int32).  Two memsets and one launch, no host wait."""
+    location, count = _heat_operands("heat_rgk", location, count)
+    _det_f32("heat_rgk", dimension=dimension)
+    _lib.require_device(angle_deg)
+    B, K, width = location.shape
+    if tuple(dimension.shape) != (B, K, 3) or tuple(angle_deg.shape) != (B, K) or angle_deg.dtype != torch.float64:
+        raise ValueError(f"heat_rgk: dimension ({B}, {K}, 3) float32 and angle_deg ({B}, {K}) float64, got {tuple(dimension.shape)}, "
+                         f"{angle_deg.dtype} {tuple(angle_deg.shape)}")
+    L, W = int(grid_lw[0]), int(grid_lw[1])
+    dev = location.device
+    make = torch.zeros if B * L * W == 0 else torch.empty
+    heat = make((B, L, W), dtype=torch.float32, device=dev)
+    n_clipped = make((B,), dtype=torch.int32, device=dev)
+    _launch("vfa_heat_rgk_f32", _lib.ptr(location), int(width), _lib.ptr(count), _lib.ptr(dimension.contiguous()),
+            _lib.ptr(angle_deg.contiguous()), B, K, L, W, float(world_size[0]), float(world_size[1]), int(kind), float(alpha), int(ratio),
+            _lib.ptr(heat), _lib.ptr(n_clipped), _lib.current_stream_handle(), tag=(B, K, L, W))
+    return heat, n_clipped
+
+
+def heat_gk(location, count, table, world_size=(1.0, 1.0), grid_lw=(1, 1), kind=0):
+    """``vfa_heat_gk_f32``: location (B, K, 2|3), count (B) int32, table (2r+1, 2r+1) float32 on the device -> heat (B, L, W) float32.
+    One memset and two launches, no host wait."""
+    location, count = _heat_operands("heat_gk", location, count)
+    _det_f32("heat_gk", table=table)
+    if table.dim() != 2 or table.shape[0] != table.shape[1] or table.shape[0] % 2 != 1:
+        raise ValueError(f"heat_gk: table must be (2r+1, 2r+1), got {tuple(table.shape)}")
+    B, K, width = location.shape
+    L, W = int(grid_lw[0]), int(grid_lw[1])
+    dev = location.device
+    heat = (torch.zeros if B * L * W == 0 else torch.empty)((B, L, W), dtype=torch.float32, device=dev)
+    ws_bytes = _lib.lib().vfa_heat_workspace_bytes(B, L, W)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    _launch("vfa_heat_gk_f32", _lib.ptr(location), int(width), _lib.ptr(count), _lib.ptr(table.contiguous()), int(table.shape[0] // 2), B, K,
+            L, W, float(world_size[0]), float(world_size[1]), int(kind), _lib.ptr(ws), ws_bytes, _lib.ptr(heat),
+            _lib.current_stream_handle(), tag=(B, K, L, W))
+    return heat
