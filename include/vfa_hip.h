@@ -859,6 +859,32 @@ int vfa_heat_rgk_f32(const float *location, int loc_width, const int *count, con
 int vfa_heat_gk_f32(const float *location, int loc_width, const int *count, const float *table, int r, int B, int K, int L, int W,
                     float world0, float world1, int kind, void *workspace, size_t workspace_bytes, float *heat, void *stream);
 
+/* ---- the front of a frame: the cameras' 8-bit frames -> the normalised float32 tensor of the trunk, no host resize ---------------
+ *                         replaces transforms.Resize + ToTensor (vfa/data/dataset.py:63, train.py:209-214) and vfanet.py:59
+ * src: N images of Hin x Win pixels, three interleaved bytes per pixel (the layout of a decoded camera frame); pixel (y, x) of
+ * image i starts at src + i * image_stride_bytes + y * row_stride_bytes + 3 * x (row_stride_bytes >= 3 * Win, any alignment).
+ * dst (N, 3, Hout, Wout) float32 contiguous, every element written.  The arithmetic is Pillow's antialiased bilinear resize of 8-bit
+ * images -- per axis integer coefficients of 22 fractional bits made in double, the horizontal pass rounded to bytes before the
+ * vertical one -- then (float)byte / 255.0f and (t - mean[c]) / std[c] with IEEE float32 divisions: BIT FOR BIT what the reference's
+ * chain computes on the host.  An axis that keeps its length is copied (its coefficients are the identity); mean 0, std 1 gives
+ * plain ToTensor.  The rules: csrc/vfa_resize.h.
+ *
+ * vfa_image_plan writes both axes' taps and the 3 x 256 table of the three channels (mean, std: 3 floats each on the DEVICE) into
+ *   workspace (vfa_image_workspace_bytes(Hin, Win, Hout, Wout) bytes, the caller's, 16-byte aligned): one small launch, once per
+ *   (sizes, mean, std).  vfa_image_frames_u8_f32 reads it: one launch, one workgroup per tile of one image, the horizontal pass into
+ *   LDS bytes, the vertical pass out of LDS; no intermediate image in memory.  Both are stream-ordered and capturable.
+ *
+ * Errors, decided before anything is launched: a non-positive length, N < 0, a NULL pointer, a short workspace, row_stride_bytes <
+ * 3 * Win, image_stride_bytes < 0: VFA_ERR_BAD_ARGUMENT; a length above VFA_IMAGE_MAX_LENGTH, an axis that shrinks by more than 8
+ * (more than VFA_IMAGE_MAX_TAPS taps), N > 65535: VFA_ERR_UNSUPPORTED (the workspace size of such lengths is 0); N == 0 returns 0. */
+#define VFA_IMAGE_MAX_TAPS 17
+#define VFA_IMAGE_MAX_LENGTH 16384
+size_t vfa_image_workspace_bytes(int Hin, int Win, int Hout, int Wout);
+int vfa_image_plan(int Hin, int Win, int Hout, int Wout, const float *mean, const float *std, void *workspace, size_t workspace_bytes,
+                   void *stream);
+int vfa_image_frames_u8_f32(const unsigned char *src, long long image_stride_bytes, long long row_stride_bytes, int N, int Hin, int Win,
+                            const void *workspace, size_t workspace_bytes, float *dst, int Hout, int Wout, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

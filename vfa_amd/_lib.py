@@ -138,6 +138,9 @@ SIGNATURES = {
                          _vp, _vp],
     "vfa_heat_gk_f32": [_vp, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_int, _vp, _c_size_t, _vp,
                         _vp],
+    "vfa_image_workspace_bytes": [_c_int, _c_int, _c_int, _c_int],
+    "vfa_image_plan": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_size_t, _vp],
+    "vfa_image_frames_u8_f32": [_vp, _c_longlong, _c_longlong, _c_int, _c_int, _c_int, _vp, _c_size_t, _vp, _c_int, _c_int, _vp],
 }
 
 _lib = None

@@ -1317,3 +1317,112 @@ def heat_gk(location, count, table, world_size=(1.0, 1.0), grid_lw=(1, 1), kind=
             L, W, float(world_size[0]), float(world_size[1]), int(kind), _lib.ptr(ws), ws_bytes, _lib.ptr(heat),
             _lib.current_stream_handle(), tag=(B, K, L, W))
     return heat
+
+
+IMAGE_MAX_TAPS, IMAGE_MAX_LENGTH = 17, 16384  # VFA_IMAGE_MAX_TAPS, VFA_IMAGE_MAX_LENGTH
+_IMAGE_PLANS = {}     # key -> _ImagePlan, in order of insertion
+_IMAGE_PLANS_KEPT = 16
+
+
+class _ImagePlan:
+    """A workspace ``vfa_image_plan`` has filled, the operands it was made from (kept alive: their identity is the key) and the
+    streams that are ordered behind the launch that filled it."""
+
+    def __init__(self, workspace, ws_bytes, operands, event, stream_id):
+        self.workspace, self.ws_bytes, self.operands, self.event, self.streams = workspace, ws_bytes, operands, event, {stream_id}
+
+
+def _image_constant(name, value, fill, dev):
+    """mean / std -> (what the plan cache compares, a (3) float32 tensor on ``dev``).  Numbers are compared by value.  A tensor is
+    compared by identity and version counter -- reading its values would be a host wait --, so an in-place update of a model's
+    buffer makes a new plan and a tensor written behind torch's back does not."""
+    if value is None:
+        value = (fill,) * 3
+    if isinstance(value, torch.Tensor):
+        if value.numel() != 3:
+            raise ValueError(f"image_frontend: {name} needs 3 values, got {tuple(value.shape)}")
+        return ("tensor", id(value), value._version), value.detach().to(device=dev, dtype=torch.float32).reshape(3).contiguous()
+    values = tuple(float(v) for v in value)
+    if len(values) != 3:
+        raise ValueError(f"image_frontend: {name} needs 3 values, got {len(values)}")
+    return values, None
+
+
+def image_taps(n_in, n_out):
+    """Taps of one axis of the resize (``vfa_resize::ksize_of``)."""
+    import math
+    return int(math.ceil(max(n_in / n_out, 1.0))) * 2 + 1
+
+
+def _image_plan(dev, sizes, mean, std):
+    """The plan of (device, sizes, mean, std): made on the current stream the first time, then kept.  Another stream waits, on the
+    device, for the launch that made it.  Under stream capture nothing is waited for and nothing is kept: a plan made before the
+    capture is read (the capture begins behind it), one made inside it belongs to the graph."""
+    mean_key, mean_t = _image_constant("mean", mean, 0.0, dev)
+    std_key, std_t = _image_constant("std", std, 1.0, dev)
+    key = (dev.index if dev.index is not None else _lib.current_device_index(), *sizes, mean_key, std_key)
+    stream = _lib.current_stream(dev)
+    capturing = torch.cuda.is_current_stream_capturing()
+    plan = _IMAGE_PLANS.get(key)
+    if plan is None:
+        if mean_t is None:
+            mean_t = torch.tensor(mean_key, dtype=torch.float32).to(dev, non_blocking=True)
+        if std_t is None:
+            std_t = torch.tensor(std_key, dtype=torch.float32).to(dev, non_blocking=True)
+        ws_bytes = _lib.lib().vfa_image_workspace_bytes(*sizes)
+        workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _launch("vfa_image_plan", *sizes, _lib.ptr(mean_t), _lib.ptr(std_t), _lib.ptr(workspace), ws_bytes, _lib.current_stream_handle(),
+                tag=sizes)
+        if capturing:
+            return _ImagePlan(workspace, ws_bytes, (mean, std, mean_t, std_t), None, stream.cuda_stream)
+        event = torch.cuda.Event()
+        event.record(stream)
+        plan = _IMAGE_PLANS[key] = _ImagePlan(workspace, ws_bytes, (mean, std, mean_t, std_t), event, stream.cuda_stream)
+        while len(_IMAGE_PLANS) > _IMAGE_PLANS_KEPT:
+            del _IMAGE_PLANS[next(iter(_IMAGE_PLANS))]
+    elif stream.cuda_stream not in plan.streams and not capturing:
+        stream.wait_event(plan.event)
+        plan.workspace.record_stream(stream)
+        plan.streams.add(stream.cuda_stream)
+    return plan
+
+
+def image_frontend(frames_u8, size=None, mean=None, std=None, out=None):
+    """``vfa_image_frames_u8_f32``: camera frames (N, H, W, 3) or (B, N, H, W, 3) uint8 on the device -> (..., 3, Hout, Wout) float32,
+    bit for bit the reference's host chain: Pillow's antialiased bilinear ``transforms.Resize(size)`` (``size = (Hout, Wout)``;
+    ``None``: no resize), ``ToTensor`` and ``(x - mean) / std`` (``None``: 0 and 1, plain ``ToTensor``).  A row pitch and an image
+    stride are taken as they are (``stride(-1) == 1``, ``stride(-2) == 3``, rows of at least ``3 W`` bytes); other layouts are
+    copied.  One launch on the current stream, no host wait; the plan (``vfa_image_plan``: the taps of both axes and the 3 x 256
+    table) is made on the first call with these (device, sizes, mean, std) and kept."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (4, 5) or frames_u8.shape[-1] != 3:
+        raise ValueError(f"image_frontend: frames (N, H, W, 3) or (B, N, H, W, 3) uint8, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+    _lib.require_device(frames_u8, out, *(t for t in (mean, std) if isinstance(t, torch.Tensor)))
+    lead, (Hin, Win) = tuple(frames_u8.shape[:-3]), frames_u8.shape[-3:-1]
+    Hout, Wout = (Hin, Win) if size is None else (int(size[0]), int(size[1]))
+    if min(Hin, Win, Hout, Wout) < 1 or max(Hin, Win, Hout, Wout) > IMAGE_MAX_LENGTH:
+        raise ValueError(f"image_frontend: lengths must be in 1 .. {IMAGE_MAX_LENGTH}, got {Hin} x {Win} -> {Hout} x {Wout}")
+    if max(image_taps(Hin, Hout), image_taps(Win, Wout)) > IMAGE_MAX_TAPS:
+        raise ValueError(f"image_frontend: {Hin} x {Win} -> {Hout} x {Wout} shrinks an axis by more than 8 (more than {IMAGE_MAX_TAPS} taps)")
+    flat = frames_u8
+    if flat.stride(-1) != 1 or (Win > 1 and flat.stride(-2) != 3) or (Hin > 1 and flat.stride(-3) < 3 * Win):
+        flat = flat.contiguous()
+    if flat.dim() == 5:
+        try:
+            flat = flat.view(-1, Hin, Win, 3)       # (one image stride for the B * N images)
+        except RuntimeError:
+            flat = flat.contiguous().view(-1, Hin, Win, 3)
+    N = flat.shape[0]
+    dev = frames_u8.device
+    if out is None:
+        out = torch.empty((*lead, 3, Hout, Wout), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (*lead, 3, Hout, Wout) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"image_frontend: out must be contiguous float32 {(*lead, 3, Hout, Wout)} on {dev}, got {out.dtype} {tuple(out.shape)}")
+    if N == 0:
+        return out
+    sizes = (int(Hin), int(Win), Hout, Wout)
+    plan = _image_plan(dev, sizes, mean, std)
+    image_stride = int(flat.stride(0)) if N > 1 else 0                # (the stride of a dimension of one element is anything)
+    row_stride = int(flat.stride(1)) if Hin > 1 else 3 * sizes[1]
+    _launch("vfa_image_frames_u8_f32", _lib.ptr(flat), image_stride, row_stride, N, sizes[0], sizes[1], _lib.ptr(plan.workspace),
+            plan.ws_bytes, _lib.ptr(out), Hout, Wout, _lib.current_stream_handle(), tag=(N, *sizes))
+    return out

@@ -138,6 +138,7 @@ class VFANet(nn.Module):
         assert mode in ("2D", "3D"), f"mode error, expect `2D` or `3D`, got{mode}"
         self.mode = mode
         self.view_reduce = check_view_reduce(view_reduce)
+        self.input_size = getattr(args, "resize_size", None)  # (H, W) uint8 frames are resized to (train.py:209-214); None: as they are
         self.base = _Trunk(_DEPTHS[base])
         if pretrained:
             load_pretrained_trunk(self.base, base)
@@ -156,21 +157,34 @@ class VFANet(nn.Module):
             self.orient_pred = nn.Sequential(nn.Conv2d(256, angle_range, 3, padding=4, dilation=4, bias=False))
             self.thtwtl_pred = _head(3)
 
+    def normalized(self, images):
+        """The trunk's input (reference vfanet.py:59).  Float images (n,3,iH,iW), resized and scaled to [0, 1] by the caller as the
+        reference's dataset does: ``(images - mean) / std``.  uint8 frames (n,H,W,3) as the cameras deliver them (``pack_frames``):
+        the reference's resize to ``input_size``, ``ToTensor`` and the normalisation in one HIP kernel (``ops.image_frontend``),
+        the bits of the host chain."""
+        if images.dtype == torch.uint8:
+            return ops.image_frontend(images, size=self.input_size, mean=self.mean, std=self.std)
+        return (images - self.mean.view(3, 1, 1)) / self.std.view(3, 1, 1)
+
+    def _empty(self, images, h, w):
+        """The (0,256,h,w) map of no cameras or no frames, float like the images (uint8 frames: like the model)."""
+        return (images if images.is_floating_point() else self.mean).new_zeros(0, 256, h, w)
+
     def laterals(self, images):
-        """images (n,3,iH,iW) -> the three (n,256,h,w) non-negative lateral maps (reference vfanet.py:59-62, 72-74)."""
-        x = (images - self.mean.view(3, 1, 1)) / self.std.view(3, 1, 1)
+        """images (n,3,iH,iW), or uint8 (n,H,W,3), -> the three (n,256,h,w) non-negative lateral maps (reference vfanet.py:59-62, 72-74)."""
+        x = self.normalized(images)
         f8, f16, f32 = self.base(x)
         return (F.relu(self.bn8(self.lat8(f8))), F.relu(self.bn16(self.lat16(f16))), F.relu(self.bn32(self.lat32(f32))))
 
     def lateral_integrals(self, images):
-        """images (n,3,iH,iW) -> the three zero-bordered channels-last integral images of the lateral maps, without
+        """images (n,3,iH,iW), or uint8 (n,H,W,3), -> the three zero-bordered channels-last integral images of the lateral maps, without
         materialising those maps (reference vfanet.py:72-74 + vfa_op.py:110, 172-173).  ONE hand-written kernel for the three
         1x1 convolutions (``ops.lateral_convs``: six bf16 MFMA products of a three-piece split, channels-last output, GroupNorm
         statistics in its epilogue) + a tiny statistics kernel; then one launch pair for the three integral images, whose row scan applies the
         GroupNorm affine and the ReLU (``vfa_integral_images_hwc_f32``).  No NCHW lateral tensor exists.
         With gradients enabled the same kernels run inside one autograd node (``vfa_op._LateralIntegrals``) whose backward goes from
         d integral straight to the trunk maps and the lat* / bn* parameters on HIP kernels."""
-        x = (images - self.mean.view(3, 1, 1)) / self.std.view(3, 1, 1)
+        x = self.normalized(images)
         if torch.is_grad_enabled():
             return vfa_op.lateral_integrals_train(self.base(x), (self.lat8, self.lat16, self.lat32), (self.bn8, self.bn16, self.bn32))
         parts = ops.lateral_convs([(feat, conv.weight, conv.bias, gn.weight, gn.bias, gn.eps) for feat, conv, gn in
@@ -180,7 +194,8 @@ class VFANet(nn.Module):
     def ortho_features(self, images, calibs, grid, distributed=False):
         """The fused BEV map (1,256,L,W) entering the heads (reference vfanet.py:64-82, 131).  images (B,N,3,iH,iW): a batch of B
         frames -> (B,256,L,W); with ONE rig (calibs (N,3,4)) in inference the whole batch is one launch of the pipelined kernel
-        (``aggregate_views(..., frames=B)``), otherwise -- calibs (B,N,3,4), gradients, distributed -- frame by frame."""
+        (``aggregate_views(..., frames=B)``), otherwise -- calibs (B,N,3,4), gradients, distributed -- frame by frame.
+        uint8 camera frames (N,H,W,3) or (B,N,H,W,3) are taken in place of the float images (``normalized``)."""
         if images.dim() == 5:
             return self._ortho_frames(images, calibs, grid, distributed)
         if distributed:
@@ -195,7 +210,7 @@ class VFANet(nn.Module):
         if self.producer_train_ok(images):
             return aggregate_views(self.vfa8, self.vfa16, self.vfa32, None, None, None, calibs, grid, (-1, 0.95),
                                    distributed=distributed, integrals=self.lateral_integrals(images))
-        lat8, lat16, lat32 = self.laterals(images) if images.shape[0] else (images.new_zeros(0, 256, 1, 1),) * 3
+        lat8, lat16, lat32 = self.laterals(images) if images.shape[0] else (self._empty(images, 1, 1),) * 3
         return aggregate_views(self.vfa8, self.vfa16, self.vfa32, lat8, lat16, lat32, calibs, grid, (-1, 0.95),
                                distributed=distributed, view_reduce=self.view_reduce)
 
@@ -215,7 +230,7 @@ class VFANet(nn.Module):
         if (B == 0 or distributed or calibs.dim() == 4 or torch.is_grad_enabled() or self.view_reduce != "sum"
                 or not (images.is_cuda and vfa_op.frame_route(mods3, N, frames=B) == "pipe_batch")):
             outs = [self.ortho_features(images[b], calibs[b] if calibs.dim() == 4 else calibs, grid, distributed) for b in range(B)]
-            return torch.cat(outs, 0) if outs else images.new_zeros(0, 256, grid.shape[-3], grid.shape[-2])
+            return torch.cat(outs, 0) if outs else self._empty(images, grid.shape[-3], grid.shape[-2])
         flat = images.reshape(B * N, *images.shape[2:])
         if FUSE_PRODUCER:
             return aggregate_views(self.vfa8, self.vfa16, self.vfa32, None, None, None, calibs, grid, (-1, 0.95),
@@ -226,6 +241,7 @@ class VFANet(nn.Module):
     def forward(self, images, calibs, grid, visualize=False, visualize_ortho=False, distributed=False, rotation_at=None):
         """images (N,3,iH,iW), calibs (N,3,4), grid (1,L,W,3) -> dict like the reference (vfanet.py:141-149).
         images (B,N,3,iH,iW): a batch of B frames, calibs (N,3,4) or (B,N,3,4); the heads run at batch B.
+        uint8 frames (N,H,W,3) / (B,N,H,W,3): the cameras' bytes, resized to ``input_size`` and normalised on the device.
         ``rotation_at``: evaluate the orientation head only where it is read (``heads``)."""
         if visualize or visualize_ortho:
             self._visualize(images, calibs, grid, boxes=visualize_ortho)
