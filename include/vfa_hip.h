@@ -885,6 +885,47 @@ int vfa_image_plan(int Hin, int Win, int Hout, int Wout, const float *mean, cons
 int vfa_image_frames_u8_f32(const unsigned char *src, long long image_stride_bytes, long long row_stride_bytes, int N, int Hin, int Win,
                             const void *workspace, size_t workspace_bytes, float *dst, int Hout, int Wout, void *stream);
 
+/* ---- the dense 3x3 convolutions of the BEV heads at inference (csrc/vfa_conv.hip; the integer rules: csrc/vfa_conv.h) -------------
+ *                         replaces the nn.Conv2d / BatchNorm2d / GroupNorm calls of vfanet.py:131-149 in eval mode
+ * All of them: stride 1, zero padding = dilation, 1 <= dilation <= 4, float32; x (B, C, L, W) is read through its four ELEMENT
+ * strides x_stride[4] (>= 0: NCHW, channels-last or a slice; never copied), out is contiguous (B, O, L, W) and every element is
+ * written.  Fixed summation order and no float atomics: the same bits on every run, and a frame gives the same bits alone and in a
+ * batch.  Stream-ordered, no host wait, capturable; workspaces are the caller's, the library keeps no state.
+ *
+ * vfa_conv3x3_pack_weights_f32: weight (O, C, 3, 3) contiguous -> `packed` (vfa_conv3x3_packed_bytes(O, C) bytes, 16-byte aligned):
+ *   the weight's absmax and its two fp16 planes scaled by a power of two (csrc/vfa_split.h).  Once per weight; C % 32 == 0.
+ * vfa_conv3x3_f32: out[b, o] = act(conv(x, weight)[b, o] * scale[o] + shift[o]); scale / shift: device vectors of O floats or NULL
+ *   (1 / 0), relu: 0 identity, otherwise max(., 0) (a NaN stays a NaN).  The product is the three-MFMA fp16 split of
+ *   csrc/vfa_split.h; the input's scale is a power of two from the absmax of the finite values of EACH frame (a pre-pass into
+ *   workspace, vfa_conv3x3_workspace_bytes(B) bytes, 4-byte aligned).  Any O >= 1.
+ * vfa_bn_fold_f32: scale = gamma / sqrt(var + eps), shift = beta + (bias - mean) * scale (O floats each, computed in float64 on the
+ *   device): eval-mode BatchNorm and the convolution's bias as the epilogue above.  gamma, beta, bias may be NULL (1, 0, 0).
+ * vfa_conv3x3_few_f32: 1 <= O <= 4, weight (O, C, 3, 3) contiguous float32, no bias, plain fmaf: per cell four chains over a
+ *   quarter of the channels each (channel-ascending, tap-ascending), merged as (p0 + p1) + (p2 + p3).  a, b: both NULL, or (B, C)
+ *   floats: every tap inside the map is read as relu(a[b, c] * x + b[b, c]) -- a GroupNorm affine and the ReLU -- and a tap
+ *   outside the map is a zero AFTER that.  C % 4 == 0.
+ * vfa_group_norm_affine_f32: per (frame, group) the mean and the biased variance of x in float64 (fixed order) ->
+ *   a[b, c] = gamma[c] * rstd, b[b, c] = beta[c] - mean * a[b, c] ((B, C) floats; gamma / beta may be NULL), the prologue of
+ *   vfa_conv3x3_few_f32.  workspace: vfa_group_norm_workspace_bytes(B, groups) bytes, 8-byte aligned.
+ *
+ * Errors, decided before anything is launched: a negative size, O < 1, dilation < 1, groups that do not divide C, a NULL required
+ * pointer, a negative stride, a short or misaligned workspace, a `packed` of another size: VFA_ERR_BAD_ARGUMENT; C % 32 != 0 (few:
+ * C % 4), dilation > 4, O > 4 (few), B or L > 65535, L * W >= 2^30: VFA_ERR_UNSUPPORTED (vfa_conv3x3_packed_bytes is 0 for such a
+ * C).  B == 0 or L * W == 0 returns 0 and writes nothing. */
+size_t vfa_conv3x3_packed_bytes(int O, int C);
+int vfa_conv3x3_pack_weights_f32(const float *weight, int O, int C, void *packed, size_t packed_bytes, void *stream);
+size_t vfa_conv3x3_workspace_bytes(int B);
+int vfa_conv3x3_f32(const float *x, const long long *x_stride, const void *packed, size_t packed_bytes, const float *scale,
+                    const float *shift, int relu, int B, int C, int L, int W, int O, int dilation, float *out, void *workspace,
+                    size_t workspace_bytes, void *stream);
+int vfa_bn_fold_f32(const float *gamma, const float *beta, const float *mean, const float *var, const float *bias, float eps, int O,
+                    float *scale, float *shift, void *stream);
+int vfa_conv3x3_few_f32(const float *x, const long long *x_stride, const float *weight, const float *a, const float *b, int B, int C, int L,
+                        int W, int O, int dilation, float *out, void *stream);
+size_t vfa_group_norm_workspace_bytes(int B, int groups);
+int vfa_group_norm_affine_f32(const float *x, const long long *x_stride, const float *gamma, const float *beta, float eps, int B, int C,
+                              int L, int W, int groups, float *a, float *b, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,14 @@ SIGNATURES = {
     "vfa_image_workspace_bytes": [_c_int, _c_int, _c_int, _c_int],
     "vfa_image_plan": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_size_t, _vp],
     "vfa_image_frames_u8_f32": [_vp, _c_longlong, _c_longlong, _c_int, _c_int, _c_int, _vp, _c_size_t, _vp, _c_int, _c_int, _vp],
+    "vfa_conv3x3_packed_bytes": [_c_int, _c_int],
+    "vfa_conv3x3_pack_weights_f32": [_vp, _c_int, _c_int, _vp, _c_size_t, _vp],
+    "vfa_conv3x3_workspace_bytes": [_c_int],
+    "vfa_conv3x3_f32": [_vp, _vp, _vp, _c_size_t, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_size_t, _vp],
+    "vfa_bn_fold_f32": [_vp, _vp, _vp, _vp, _vp, _c_float, _c_int, _vp, _vp, _vp],
+    "vfa_conv3x3_few_f32": [_vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp],
+    "vfa_group_norm_workspace_bytes": [_c_int, _c_int],
+    "vfa_group_norm_affine_f32": [_vp, _vp, _vp, _vp, _c_float, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_size_t, _vp],
 }
 
 _lib = None

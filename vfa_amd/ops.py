@@ -1426,3 +1426,163 @@ def image_frontend(frames_u8, size=None, mean=None, std=None, out=None):
     _launch("vfa_image_frames_u8_f32", _lib.ptr(flat), image_stride, row_stride, N, sizes[0], sizes[1], _lib.ptr(plan.workspace),
             plan.ws_bytes, _lib.ptr(out), Hout, Wout, _lib.current_stream_handle(), tag=(N, *sizes))
     return out
+
+
+_CONV_KEPT = {}       # key -> _ConvKept: packed weights and folded BatchNorm vectors, in order of insertion
+_CONV_KEPT_MAX = 32
+
+
+class _ConvKept:
+    """Device tensors made from parameters by one launch (``vfa_conv3x3_pack_weights_f32``, ``vfa_bn_fold_f32``), the parameters they
+    were made from (kept alive: their identity is the key) and the streams ordered behind that launch."""
+
+    def __init__(self, tensors, operands, event, stream_id):
+        self.tensors, self.operands, self.event, self.streams = tensors, operands, event, {stream_id}
+
+
+def _conv_kept(kind, operands, extra, dev, make):
+    """``make()`` once per (kind, identity and version counter of every operand, extra), like ``_image_plan``: an in-place update of a
+    parameter makes a new entry.  Under stream capture nothing is waited for and nothing is kept."""
+    key = (kind, dev.index if dev.index is not None else _lib.current_device_index(), extra,
+           *((id(t), t._version) if t is not None else None for t in operands))
+    stream = _lib.current_stream(dev)
+    capturing = torch.cuda.is_current_stream_capturing()
+    kept = _CONV_KEPT.get(key)
+    if kept is None:
+        tensors = make()
+        if capturing:
+            return tensors
+        event = torch.cuda.Event()
+        event.record(stream)
+        kept = _CONV_KEPT[key] = _ConvKept(tensors, operands, event, stream.cuda_stream)
+        while len(_CONV_KEPT) > _CONV_KEPT_MAX:
+            del _CONV_KEPT[next(iter(_CONV_KEPT))]
+    elif stream.cuda_stream not in kept.streams and not capturing:
+        stream.wait_event(kept.event)
+        for t in kept.tensors:
+            t.record_stream(stream)
+        kept.streams.add(stream.cuda_stream)
+    return kept.tensors
+
+
+def _conv_operands(name, x, weight, *more):
+    """What the dense convolutions share: device float32 operands, inference only -> (stride array, (B, C, L, W, O))."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, *more)):
+        raise ValueError(f"{name}: inference only -- an operand requires grad while gradients are enabled (use torch.no_grad())")
+    _lib.require_device(x, weight, *more)
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise ValueError(f"{name}: x must be float32 (B, C, L, W), got {x.dtype} {tuple(x.shape)}")
+    B, C, L, W = x.shape
+    if weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[1:]) != (C, 3, 3):
+        raise ValueError(f"{name}: weight must be float32 (O, {C}, 3, 3), got {weight.dtype} {tuple(weight.shape)}")
+    for t in more:
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"{name}: every operand must be float32, got {t.dtype}")
+    return (ctypes.c_longlong * 4)(*x.stride()), (B, C, L, W, weight.shape[0])
+
+
+def conv3x3_packed_weight(weight):
+    """The pre-split fp16 planes of a (O, C, 3, 3) weight (``vfa_conv3x3_pack_weights_f32``), kept by the weight's identity and version."""
+    O, C = int(weight.shape[0]), int(weight.shape[1])
+    nbytes = _lib.lib().vfa_conv3x3_packed_bytes(O, C)
+    if nbytes == 0:
+        raise ValueError(f"conv3x3: C must be a multiple of 32, got weight {tuple(weight.shape)}")
+
+    def make():
+        w = weight.detach().contiguous()
+        packed = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+        _launch("vfa_conv3x3_pack_weights_f32", _lib.ptr(w), O, C, _lib.ptr(packed), nbytes, _lib.current_stream_handle(), tag=(O, C))
+        return (packed,)
+    return _conv_kept("pack", (weight,), None, weight.device, make)[0], nbytes
+
+
+def bn_fold(bn_weight, bn_bias, running_mean, running_var, eps, bias=None):
+    """Eval-mode BatchNorm behind a convolution with ``bias`` as a per-channel epilogue (``vfa_bn_fold_f32``): ``scale = weight /
+    sqrt(running_var + eps)``, ``shift = bn_bias + (bias - running_mean) * scale``, made on the device and kept by the identity and
+    version of the five tensors."""
+    _lib.require_device(running_mean, running_var, bn_weight, bn_bias, bias)
+    O, dev = running_mean.numel(), running_mean.device
+    operands = (bn_weight, bn_bias, running_mean, running_var, bias)
+    for t in operands:
+        if t is not None and (t.dtype != torch.float32 or t.numel() != O):
+            raise ValueError(f"bn_fold: every operand must be float32 with {O} values, got {t.dtype} {tuple(t.shape)}")
+
+    def make():
+        ops_c = [None if t is None else t.detach().contiguous() for t in operands]
+        scale, shift = torch.empty(O, dtype=torch.float32, device=dev), torch.empty(O, dtype=torch.float32, device=dev)
+        _launch("vfa_bn_fold_f32", *(_lib.ptr(t) for t in ops_c), float(eps), O, _lib.ptr(scale), _lib.ptr(shift),
+                _lib.current_stream_handle(), tag=(O,))
+        return scale, shift
+    return _conv_kept("bn", operands, float(eps), dev, make)
+
+
+def conv3x3(x, weight, dilation=1, scale=None, shift=None, relu=False):
+    """``act(F.conv2d(x, weight, padding=dilation, dilation=dilation) * scale[o] + shift[o])`` at inference on the HIP kernel
+    (``vfa_conv3x3_f32``): x (B, C, L, W) float32 read through its strides (NCHW, channels-last or a slice, never copied), C a
+    multiple of 32, weight (O, C, 3, 3), dilation 1..4, scale / shift (O) device vectors or None (a bias is ``shift``; eval-mode
+    BatchNorm: ``bn_fold``), relu -> (B, O, L, W) contiguous.  The three-product fp16 split of fp32 operands on the matrix pipe,
+    per-frame power-of-two scales: the same bits on every run, alone and in a batch; no host wait, capturable.  The pre-split weight
+    is kept by the weight's identity and version."""
+    stride, (B, C, L, W, O) = _conv_operands("conv3x3", x, weight, scale, shift)
+    if not 1 <= int(dilation) <= 4:
+        raise ValueError(f"conv3x3: dilation must be 1..4, got {dilation}")
+    for name, t in (("scale", scale), ("shift", shift)):
+        if t is not None and t.numel() != O:
+            raise ValueError(f"conv3x3: {name} must have {O} values, got {tuple(t.shape)}")
+    packed, nbytes = conv3x3_packed_weight(weight)
+    scale = None if scale is None else scale.detach().contiguous()
+    shift = None if shift is None else shift.detach().contiguous()
+    out = torch.empty((B, O, L, W), dtype=torch.float32, device=x.device)
+    if out.numel() == 0:
+        return out
+    ws_bytes = _lib.lib().vfa_conv3x3_workspace_bytes(B)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    _launch("vfa_conv3x3_f32", _lib.ptr(x), stride, _lib.ptr(packed), nbytes, _lib.ptr(scale), _lib.ptr(shift), int(bool(relu)), B, C, L, W,
+            O, int(dilation), _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(), tag=(B, C, L, W, O, int(dilation)))
+    return out
+
+
+def conv3x3_few(x, weight, dilation=1, affine=None):
+    """``F.conv2d(x', weight, padding=dilation, dilation=dilation)`` for 1..4 outputs without bias, in fp32 ``fmaf``
+    (``vfa_conv3x3_few_f32``).  ``affine = (a, b)``, both (B, C): ``x' = relu(a[b, c] * x + b[b, c])`` applied as the taps are read
+    (``group_norm_affine``: GroupNorm and ReLU without writing the normalised map; the zero padding is applied to ``x'``);
+    ``None``: ``x' = x``.  x is read through its strides -> (B, O, L, W) contiguous."""
+    a, b = (None, None) if affine is None else affine
+    stride, (B, C, L, W, O) = _conv_operands("conv3x3_few", x, weight, a, b)
+    if not 1 <= O <= 4 or not 1 <= int(dilation) <= 4 or C % 4:
+        raise ValueError(f"conv3x3_few: 1..4 outputs, dilation 1..4 and C a multiple of 4, got weight {tuple(weight.shape)}, dilation {dilation}")
+    if affine is not None:
+        if tuple(a.shape) != (B, C) or tuple(b.shape) != (B, C):
+            raise ValueError(f"conv3x3_few: affine must be two ({B}, {C}) tensors, got {tuple(a.shape)} and {tuple(b.shape)}")
+        a, b = a.contiguous(), b.contiguous()
+    w = weight.detach().contiguous()
+    out = torch.empty((B, O, L, W), dtype=torch.float32, device=x.device)
+    if out.numel():
+        _launch("vfa_conv3x3_few_f32", _lib.ptr(x), stride, _lib.ptr(w), _lib.ptr(a), _lib.ptr(b), B, C, L, W, O, int(dilation),
+                _lib.ptr(out), _lib.current_stream_handle(), tag=(B, C, L, W, O, int(dilation)))
+    return out
+
+
+def group_norm_affine(x, groups, weight, bias, eps):
+    """GroupNorm of x (B, C, L, W) as a per (frame, channel) affine (``vfa_group_norm_affine_f32``): ``F.group_norm(x, groups, weight,
+    bias, eps) == a[b, c] * x + b[b, c]`` with the statistics of each (frame, group) summed in float64 in a fixed order ->
+    (a, b), both (B, C) float32: the prologue of ``conv3x3_few``."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias)):
+        raise ValueError("group_norm_affine: inference only -- an operand requires grad while gradients are enabled (use torch.no_grad())")
+    _lib.require_device(x, weight, bias)
+    if x.dtype != torch.float32 or x.dim() != 4 or int(groups) < 1 or x.shape[1] % int(groups):
+        raise ValueError(f"group_norm_affine: x must be float32 (B, C, L, W) with groups | C, got {x.dtype} {tuple(x.shape)}, groups {groups}")
+    B, C, L, W = x.shape
+    for t in (weight, bias):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != C):
+            raise ValueError(f"group_norm_affine: weight / bias must be float32 ({C}), got {t.dtype} {tuple(t.shape)}")
+    weight = None if weight is None else weight.detach().contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    a, b = torch.empty((B, C), dtype=torch.float32, device=x.device), torch.empty((B, C), dtype=torch.float32, device=x.device)
+    if x.numel() == 0:
+        raise ValueError("group_norm_affine: an empty map has no statistics")
+    ws_bytes = _lib.lib().vfa_group_norm_workspace_bytes(B, int(groups))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    _launch("vfa_group_norm_affine_f32", _lib.ptr(x), (ctypes.c_longlong * 4)(*x.stride()), _lib.ptr(weight), _lib.ptr(bias), float(eps), B, C,
+            L, W, int(groups), _lib.ptr(a), _lib.ptr(b), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(), tag=(B, C, L, W, int(groups)))
+    return a, b

@@ -11,6 +11,9 @@ Multi-GPU (``distributed=True``): each rank runs backbone + laterals + projectio
 
 ``view_reduce="max"`` fuses the cameras by an elementwise maximum instead of the reference's sum (``aggregate_views``; DESIGN.md
 4.9).  It is a plain attribute, not a buffer: the ``state_dict`` keys stay the reference's.
+
+``head_convs="hip"`` (a plain attribute too; default ``"library"``) runs the dense 3x3 convolutions of the BEV heads at inference on
+the HIP kernels of ``csrc/vfa_conv.hip`` from the same parameters (``heads``).
 """
 import glob
 import os
@@ -35,6 +38,8 @@ FUSE_PRODUCER_TRAIN = os.environ.get("VFA_AMD_FUSE_PRODUCER_TRAIN", "0") == "1"
 # ``pretrained=True`` (the default of the reference's train.py:90): the reference downloads the torchvision ImageNet
 # checkpoint (resnet.py:155-159, 170-172).  There is no network on the MI355X boxes, so the file is looked up locally.
 PRETRAINED_ENV = "VFA_AMD_PRETRAINED"
+# Who runs the dense 3x3 convolutions of the BEV heads (``VFANet.head_convs``, ``VFANet.heads(convs=...)``)
+HEAD_CONVS = ("library", "hip")
 
 
 def _find_pretrained(base):
@@ -138,6 +143,7 @@ class VFANet(nn.Module):
         assert mode in ("2D", "3D"), f"mode error, expect `2D` or `3D`, got{mode}"
         self.mode = mode
         self.view_reduce = check_view_reduce(view_reduce)
+        self.head_convs = "library"  # or "hip" (``heads``); a plain attribute like ``view_reduce``: no ``state_dict`` key
         self.input_size = getattr(args, "resize_size", None)  # (H, W) uint8 frames are resized to (train.py:209-214); None: as they are
         self.base = _Trunk(_DEPTHS[base])
         if pretrained:
@@ -276,8 +282,37 @@ class VFANet(nn.Module):
                 if boxes:
                     self.vfa8.visualize_cube(one[0], calibs[cam], grid)
 
-    def heads(self, topdown, rotation_at=None):
+    def _hip_convs_ok(self, topdown):
+        """``head_convs = "hip"`` covers inference on the reference's widths: eval mode, no gradients, a float32 CUDA map of 256
+        channels, BatchNorm layers with running statistics.  Anything else runs the library path, as ``FUSE_PRODUCER`` does."""
+        return (not self.training and not torch.is_grad_enabled() and topdown.is_cuda and topdown.dtype == torch.float32
+                and topdown.dim() == 4 and topdown.shape[1] == 256 and topdown.numel() > 0
+                and all(bn.running_mean is not None and not bn.training for bn in (self.fuse[1], self.fuse[4])))
+
+    def _hip_head(self, topdown, head):
+        """``Conv2d(256, 256, 3) -> GroupNorm -> ReLU -> Conv2d(256, cout, 3)`` (``_head``): the dense kernel with the bias as its
+        epilogue, the GroupNorm statistics as a per (frame, channel) affine, and that affine with the ReLU as the prologue of the
+        few-output kernel -- the normalised map is never written."""
+        conv, gn, _, last = head
+        y = ops.conv3x3(topdown, conv.weight, conv.dilation[0], shift=conv.bias)
+        affine = ops.group_norm_affine(y, gn.num_groups, gn.weight, gn.bias, gn.eps)
+        return ops.conv3x3_few(y, last.weight, last.dilation[0], affine=affine)
+
+    def _hip_fuse(self, topdown):
+        """``fuse`` with eval-mode BatchNorm, the bias and the ReLU folded into the dense kernel's epilogue."""
+        x = topdown
+        for conv, bn in ((self.fuse[0], self.fuse[1]), (self.fuse[3], self.fuse[4])):
+            scale, shift = ops.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, conv.bias)
+            x = ops.conv3x3(x, conv.weight, conv.dilation[0], scale=scale, shift=shift, relu=True)
+        return x
+
+    def heads(self, topdown, rotation_at=None, convs=None):
         """The BEV heads on the fused map (reference vfanet.py:131-149).
+
+        ``convs`` (``None``: the attribute ``head_convs``): ``"library"`` runs the dense convolutions of ``fuse``, ``map_classifier``,
+        ``tytx_pred`` and ``thtwtl_pred`` as the modules they are; ``"hip"`` runs them at inference on ``ops.conv3x3`` /
+        ``ops.conv3x3_few`` / ``ops.group_norm_affine`` -- the same function of the same parameters up to the summation order
+         -- where ``_hip_convs_ok`` holds, and the library path otherwise.
 
         ``rotation_at`` (3D only, ``ValueError`` in 2D) evaluates ``orient_pred`` -- the largest layer of the heads, read at a few
         dozen cells -- only where it is read, on ``ops.conv3x3_at_cells`` instead of a dense convolution; the other heads are the
@@ -288,10 +323,20 @@ class VFANet(nn.Module):
         ``BEVDecoder.decode_fused`` takes the rotation at the cells it selects."""
         if rotation_at is not None and self.mode != "3D":
             raise ValueError("VFANet.heads: rotation_at needs mode 3D (a 2D model has no orientation head)")
-        fused = self.fuse(topdown)
-        out = {"heatmap": self.map_classifier(fused), "loc_offset": self.tytx_pred(topdown).permute(0, 2, 3, 1)}
+        convs = self.head_convs if convs is None else convs
+        if convs not in HEAD_CONVS:
+            raise ValueError(f"VFANet.heads: convs is one of {HEAD_CONVS}, got {convs!r}")
+        hip = convs == "hip" and self._hip_convs_ok(topdown)
+        if hip:
+            fused = self._hip_fuse(topdown)
+            conv = self.map_classifier[0]
+            out = {"heatmap": ops.conv3x3_few(fused, conv.weight, conv.dilation[0]),
+                   "loc_offset": self._hip_head(topdown, self.tytx_pred).permute(0, 2, 3, 1)}
+        else:
+            fused = self.fuse(topdown)
+            out = {"heatmap": self.map_classifier(fused), "loc_offset": self.tytx_pred(topdown).permute(0, 2, 3, 1)}
         if self.mode == "3D":
-            out["dim_offset"] = self.thtwtl_pred(topdown).permute(0, 2, 3, 1)
+            out["dim_offset"] = (self._hip_head(topdown, self.thtwtl_pred) if hip else self.thtwtl_pred(topdown)).permute(0, 2, 3, 1)
             conv = self.orient_pred[0]
             if rotation_at is None:
                 out["rotation"] = self.orient_pred(fused).permute(0, 2, 3, 1)
