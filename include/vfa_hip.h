@@ -926,6 +926,39 @@ size_t vfa_group_norm_workspace_bytes(int B, int groups);
 int vfa_group_norm_affine_f32(const float *x, const long long *x_stride, const float *gamma, const float *beta, float eps, int B, int C,
                               int L, int W, int groups, float *a, float *b, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the residual stages of the ResNet trunk at inference (csrc/vfa_trunk.hip; the integer rules: csrc/vfa_trunk.h) ----------------
+ *                         replaces the nn.Conv2d / GroupNorm / ReLU calls of a block, resnet.py:26-57, in eval mode
+ * The dense kernel above with a stride, one or nine taps and a prologue; float32; x (B, C, L, W) is read through its four ELEMENT
+ * strides x_stride[4] (>= 0, never copied).  Fixed summation order and no float atomics: the same bits on every run, and an image
+ * gives the same bits alone and in a batch.  Stream-ordered, no host wait, capturable; workspaces are the caller's, the library
+ * keeps no state.
+ *
+ * vfa_trunk_pack_weights_f32: weight (O, C, 3, 3) with taps 9 or (O, C, 1, 1) with taps 1, contiguous -> `packed`
+ *   (vfa_trunk_packed_bytes(O, C, taps) bytes, 16-byte aligned): the weight's absmax and its two fp16 planes scaled by a power of
+ *   two, in the slices of csrc/vfa_conv.h with `taps` slices per (output tile, chunk).  Once per weight; C % 32 == 0.
+ * vfa_trunk_conv_f32: out (B, O, Lo, Wo) contiguous, Lo = (L - 1) / stride + 1, Wo = (W - 1) / stride + 1, every element written:
+ *   the raw convolution, without bias.  taps 9: 3 x 3, zero padding 1; taps 1: 1 x 1, no padding; stride 1 or 2.  a, b: both NULL,
+ *   or (B, C) floats: every tap inside the map reads max(fmaf(a[b, c], x, b[b, c]), 0) -- a GroupNorm affine and the ReLU, the
+ *   normalised map is never written -- and a tap outside the map is a zero AFTER that.  The product is the three-MFMA fp16 split of
+ *   csrc/vfa_split.h; the input's scale is a power of two from the absmax of the finite values the products see (after the
+ *   prologue; with one tap at the strided positions) of EACH image, a pre-pass into workspace (vfa_trunk_workspace_bytes(B) bytes,
+ *   4-byte aligned).  With C > 256 the two halves of the channels are summed in separate fp32 chains and added once.  Any O >= 1.
+ * vfa_residual_join_f32: out = max(fmaf(a[b, c], y, b[b, c]) + shortcut, 0) with shortcut = r, or fmaf(ra[b, c], r, rb[b, c]) where
+ *   ra, rb are given (both or neither); y, r, out contiguous (B, C, L, W), a, b, ra, rb (B, C) floats; out may be y.  One rounding
+ *   per written operation; a NaN stays a NaN.
+ *
+ * Errors, decided before anything is launched: a negative size, O < 1, taps other than 1 or 9, a stride other than 1 or 2, one of
+ * a / b (ra / rb) without the other, a NULL required pointer, a negative element stride, a short or misaligned workspace, a `packed`
+ * of another size: VFA_ERR_BAD_ARGUMENT; C % 32 != 0, B or L > 65535, L * W >= 2^30: VFA_ERR_UNSUPPORTED (vfa_trunk_packed_bytes
+ * is 0 for such a C or such taps).  An empty problem (B == 0 or L * W == 0; the join: C == 0 too) returns 0 and writes nothing. */
+size_t vfa_trunk_packed_bytes(int O, int C, int taps);
+int vfa_trunk_pack_weights_f32(const float *weight, int O, int C, int taps, void *packed, size_t packed_bytes, void *stream);
+size_t vfa_trunk_workspace_bytes(int B);
+int vfa_trunk_conv_f32(const float *x, const long long *x_stride, const void *packed, size_t packed_bytes, const float *a, const float *b, int B,
+                       int C, int L, int W, int O, int taps, int stride, float *out, void *workspace, size_t workspace_bytes, void *stream);
+int vfa_residual_join_f32(const float *y, const float *a, const float *b, const float *r, const float *ra, const float *rb, int B, int C, int L,
+                          int W, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

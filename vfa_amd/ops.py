@@ -1429,7 +1429,10 @@ def image_frontend(frames_u8, size=None, mean=None, std=None, out=None):
 
 
 _CONV_KEPT = {}       # key -> _ConvKept: packed weights and folded BatchNorm vectors, in order of insertion
-_CONV_KEPT_MAX = 32
+# A ResNet-34 trunk keeps 35 packs (``trunk_conv``; the stem is not packed) beside the heads' 10 entries, and a model must not re-pack
+# per frame.  An entry holds its source parameters too (their identity is the key), so up to this many weights of models no longer in
+# use, with their packs, stay on the device until newer entries push them out.
+_CONV_KEPT_MAX = 128
 
 
 class _ConvKept:
@@ -1465,7 +1468,7 @@ def _conv_kept(kind, operands, extra, dev, make):
     return kept.tensors
 
 
-def _conv_operands(name, x, weight, *more):
+def _conv_operands(name, x, weight, *more, kernels=(3,)):
     """What the dense convolutions share: device float32 operands, inference only -> (stride array, (B, C, L, W, O))."""
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, *more)):
         raise ValueError(f"{name}: inference only -- an operand requires grad while gradients are enabled (use torch.no_grad())")
@@ -1473,8 +1476,8 @@ def _conv_operands(name, x, weight, *more):
     if x.dtype != torch.float32 or x.dim() != 4:
         raise ValueError(f"{name}: x must be float32 (B, C, L, W), got {x.dtype} {tuple(x.shape)}")
     B, C, L, W = x.shape
-    if weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[1:]) != (C, 3, 3):
-        raise ValueError(f"{name}: weight must be float32 (O, {C}, 3, 3), got {weight.dtype} {tuple(weight.shape)}")
+    if weight.dtype != torch.float32 or weight.dim() != 4 or all(tuple(weight.shape[1:]) != (C, k, k) for k in kernels):
+        raise ValueError(f"{name}: weight must be float32 {' or '.join(f'(O, {C}, {k}, {k})' for k in kernels)}, got {weight.dtype} {tuple(weight.shape)}")
     for t in more:
         if t is not None and t.dtype != torch.float32:
             raise ValueError(f"{name}: every operand must be float32, got {t.dtype}")
@@ -1586,3 +1589,77 @@ def group_norm_affine(x, groups, weight, bias, eps):
     _launch("vfa_group_norm_affine_f32", _lib.ptr(x), (ctypes.c_longlong * 4)(*x.stride()), _lib.ptr(weight), _lib.ptr(bias), float(eps), B, C,
             L, W, int(groups), _lib.ptr(a), _lib.ptr(b), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(), tag=(B, C, L, W, int(groups)))
     return a, b
+
+
+def trunk_packed_weight(weight):
+    """The pre-split fp16 planes of a (O, C, 3, 3) or (O, C, 1, 1) weight (``vfa_trunk_pack_weights_f32``), kept by the weight's
+    identity and version like ``conv3x3_packed_weight`` (the same table: ``_CONV_KEPT_MAX`` holds a ResNet-34 trunk and the heads)."""
+    O, C, taps = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2]) * int(weight.shape[3])
+    nbytes = _lib.lib().vfa_trunk_packed_bytes(O, C, taps)
+    if nbytes == 0:
+        raise ValueError(f"trunk_conv: C must be a multiple of 32 and the weight 3 x 3 or 1 x 1, got weight {tuple(weight.shape)}")
+
+    def make():
+        w = weight.detach().contiguous()
+        packed = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+        _launch("vfa_trunk_pack_weights_f32", _lib.ptr(w), O, C, taps, _lib.ptr(packed), nbytes, _lib.current_stream_handle(), tag=(O, C, taps))
+        return (packed,)
+    return _conv_kept("trunk_pack", (weight,), None, weight.device, make)[0], nbytes
+
+
+def trunk_conv(x, weight, stride=1, affine=None):
+    """``F.conv2d(x', weight, stride=stride, padding=1)`` for a (O, C, 3, 3) weight, ``F.conv2d(x', weight, stride=stride)`` for a
+    (O, C, 1, 1) weight, without bias, at inference on the HIP kernel (``vfa_trunk_conv_f32``): the raw convolution (B, O, Lo, Wo)
+    contiguous.  x (B, C, L, W) float32 read through its strides, C a multiple of 32, stride 1 or 2.  ``affine = (a, b)``, both
+    (B, C): ``x' = relu(a[b, c] * x + b[b, c])`` applied as the taps are read (``group_norm_affine``; the zero padding is applied to
+    ``x'``); ``None``: ``x' = x``.  The three-product fp16 split of ``conv3x3`` with a per-image power-of-two scale taken after the
+    prologue: the same bits on every run, alone and in a batch; no host wait, capturable."""
+    a, b = (None, None) if affine is None else affine
+    stride_arr, (B, C, L, W, O) = _conv_operands("trunk_conv", x, weight, a, b, kernels=(3, 1))
+    if int(stride) not in (1, 2):
+        raise ValueError(f"trunk_conv: stride must be 1 or 2, got {stride}")
+    if affine is not None:
+        if tuple(a.shape) != (B, C) or tuple(b.shape) != (B, C):
+            raise ValueError(f"trunk_conv: affine must be two ({B}, {C}) tensors, got {tuple(a.shape)} and {tuple(b.shape)}")
+        a, b = a.contiguous(), b.contiguous()
+    taps = int(weight.shape[2]) * int(weight.shape[3])
+    packed, nbytes = trunk_packed_weight(weight)
+    Lo, Wo = ((L - 1) // int(stride) + 1, (W - 1) // int(stride) + 1) if L and W else (0, 0)
+    out = torch.empty((B, O, Lo, Wo), dtype=torch.float32, device=x.device)
+    if out.numel() == 0:
+        return out
+    ws_bytes = _lib.lib().vfa_trunk_workspace_bytes(B)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    _launch("vfa_trunk_conv_f32", _lib.ptr(x), stride_arr, _lib.ptr(packed), nbytes, _lib.ptr(a), _lib.ptr(b), B, C, L, W, O, taps, int(stride),
+            _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(), tag=(B, C, L, W, O, taps, int(stride)))
+    return out
+
+
+def residual_join(y, affine, shortcut, shortcut_affine=None, out=None):
+    """The end of a residual block (``vfa_residual_join_f32``): ``relu(a[b, c] * y + b[b, c] + s)`` with ``s = shortcut``, or
+    ``ra[b, c] * shortcut + rb[b, c]`` with ``shortcut_affine = (ra, rb)`` -- the GroupNorm affines of ``group_norm_affine`` applied as
+    the maps are read.  y and shortcut (B, C, L, W) contiguous float32, the affines (B, C); ``out``: ``None`` (a new tensor) or ``y``
+    (in place).  One rounding per operation: fmaf, fmaf, add, max; a NaN stays a NaN."""
+    a, b = affine
+    ra, rb = (None, None) if shortcut_affine is None else shortcut_affine
+    operands = (y, a, b, shortcut, ra, rb)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands):
+        raise ValueError("residual_join: inference only -- an operand requires grad while gradients are enabled (use torch.no_grad())")
+    _lib.require_device(*operands)
+    if y.dtype != torch.float32 or y.dim() != 4 or shortcut.dtype != torch.float32 or shortcut.shape != y.shape:
+        raise ValueError(f"residual_join: y and shortcut must be float32 (B, C, L, W) of one shape, got {tuple(y.shape)} and {tuple(shortcut.shape)}")
+    if not y.is_contiguous() or not shortcut.is_contiguous():
+        raise ValueError("residual_join: y and shortcut must be contiguous")
+    B, C, L, W = y.shape
+    for t in (a, b, ra, rb):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (B, C)):
+            raise ValueError(f"residual_join: an affine is two float32 ({B}, {C}) tensors, got {t.dtype} {tuple(t.shape)}")
+    if out is not None and out is not y:
+        raise ValueError("residual_join: out is None or y")
+    a, b = a.contiguous(), b.contiguous()
+    ra, rb = (None, None) if ra is None else (ra.contiguous(), rb.contiguous())
+    out = torch.empty_like(y) if out is None else out
+    if out.numel():
+        _launch("vfa_residual_join_f32", _lib.ptr(y), _lib.ptr(a), _lib.ptr(b), _lib.ptr(shortcut), _lib.ptr(ra), _lib.ptr(rb), B, C, L, W,
+                _lib.ptr(out), _lib.current_stream_handle(), tag=(B, C, L, W))
+    return out

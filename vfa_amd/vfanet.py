@@ -14,6 +14,10 @@ Multi-GPU (``distributed=True``): each rank runs backbone + laterals + projectio
 
 ``head_convs="hip"`` (a plain attribute too; default ``"library"``) runs the dense 3x3 convolutions of the BEV heads at inference on
 the HIP kernels of ``csrc/vfa_conv.hip`` from the same parameters (``heads``).
+
+``trunk_convs="hip"`` (the same kind of attribute; default ``"library"``) runs the residual stages ``layer1`` .. ``layer4`` of the
+ResNet trunk at inference on the HIP kernels of ``csrc/vfa_trunk.hip`` from the same parameters (``trunk``); the stem
+stays the library's.
 """
 import glob
 import os
@@ -40,6 +44,8 @@ FUSE_PRODUCER_TRAIN = os.environ.get("VFA_AMD_FUSE_PRODUCER_TRAIN", "0") == "1"
 PRETRAINED_ENV = "VFA_AMD_PRETRAINED"
 # Who runs the dense 3x3 convolutions of the BEV heads (``VFANet.head_convs``, ``VFANet.heads(convs=...)``)
 HEAD_CONVS = ("library", "hip")
+# Who runs the residual stages of the trunk (``VFANet.trunk_convs``, ``VFANet.trunk``)
+TRUNK_CONVS = ("library", "hip")
 
 
 def _find_pretrained(base):
@@ -103,6 +109,22 @@ class _Block(nn.Module):
         y = self.bn2(self.conv2(y))
         return F.relu(y + (x if self.downsample is None else self.downsample(x)), inplace=True)
 
+    def forward_hip(self, x):
+        """``forward`` at inference on ``ops.trunk_conv`` / ``ops.group_norm_affine`` / ``ops.residual_join``: a GroupNorm is a per
+        (image, channel) affine that its consumer applies as it reads, so no normalised map is written -- three or four raw
+        convolutions and one join per block.  The same function of the same parameters up to the summation order."""
+        stride = self.conv1.stride[0]
+        y1 = ops.trunk_conv(x, self.conv1.weight, stride)
+        y2 = ops.trunk_conv(y1, self.conv2.weight, 1, affine=_gn_affine(y1, self.bn1))
+        if self.downsample is None:
+            return ops.residual_join(y2, _gn_affine(y2, self.bn2), x.contiguous(), out=y2)
+        yd = ops.trunk_conv(x, self.downsample[0].weight, stride)
+        return ops.residual_join(y2, _gn_affine(y2, self.bn2), yd, _gn_affine(yd, self.downsample[1]), out=y2)
+
+
+def _gn_affine(y, gn):
+    return ops.group_norm_affine(y, gn.num_groups, gn.weight, gn.bias, gn.eps)
+
 
 class _Trunk(nn.Module):
     """ResNet-18/34 trunk returning the stride-8/16/32 maps (reference resnet.py:95-147)."""
@@ -126,6 +148,17 @@ class _Trunk(nn.Module):
         f16 = self.layer3(f8)
         return f8, f16, self.layer4(f16)
 
+    def forward_hip(self, x):
+        """``forward`` with the residual stages on the HIP kernels (``_Block.forward_hip``); the stem -- a 7 x 7 stride-2
+        convolution of three channels, GroupNorm, ReLU and the max pooling -- is the library's."""
+        x = F.max_pool2d(F.relu(self.bn1(self.conv1(x)), inplace=True), 3, stride=2, padding=1)
+        maps = []
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for block in layer:
+                x = block.forward_hip(x)
+            maps.append(x)
+        return maps[1], maps[2], maps[3]
+
 
 _DEPTHS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3)}
 
@@ -144,6 +177,7 @@ class VFANet(nn.Module):
         self.mode = mode
         self.view_reduce = check_view_reduce(view_reduce)
         self.head_convs = "library"  # or "hip" (``heads``); a plain attribute like ``view_reduce``: no ``state_dict`` key
+        self.trunk_convs = "library"  # or "hip" (``trunk``); the same kind of attribute
         self.input_size = getattr(args, "resize_size", None)  # (H, W) uint8 frames are resized to (train.py:209-214); None: as they are
         self.base = _Trunk(_DEPTHS[base])
         if pretrained:
@@ -176,10 +210,22 @@ class VFANet(nn.Module):
         """The (0,256,h,w) map of no cameras or no frames, float like the images (uint8 frames: like the model)."""
         return (images if images.is_floating_point() else self.mean).new_zeros(0, 256, h, w)
 
+    def trunk(self, x):
+        """The normalised images (n,3,iH,iW) -> the trunk's maps (f8, f16, f32), contiguous NCHW float32.  ``trunk_convs``:
+        ``"library"`` is ``self.base(x)``; ``"hip"`` runs ``layer1`` .. ``layer4`` on the kernels of ``csrc/vfa_trunk.hip``
+        (``_Trunk.forward_hip``) where the model is in eval mode, gradients are off and ``x`` is a float32 CUDA tensor with at least
+        one image, and is ``self.base(x)`` anywhere else."""
+        if self.trunk_convs not in TRUNK_CONVS:
+            raise ValueError(f"VFANet.trunk: trunk_convs is one of {TRUNK_CONVS}, got {self.trunk_convs!r}")
+        if (self.trunk_convs == "hip" and not self.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
+                and x.dim() == 4 and x.numel() > 0):
+            return self.base.forward_hip(x)
+        return self.base(x)
+
     def laterals(self, images):
         """images (n,3,iH,iW), or uint8 (n,H,W,3), -> the three (n,256,h,w) non-negative lateral maps (reference vfanet.py:59-62, 72-74)."""
         x = self.normalized(images)
-        f8, f16, f32 = self.base(x)
+        f8, f16, f32 = self.trunk(x)
         return (F.relu(self.bn8(self.lat8(f8))), F.relu(self.bn16(self.lat16(f16))), F.relu(self.bn32(self.lat32(f32))))
 
     def lateral_integrals(self, images):
@@ -192,9 +238,9 @@ class VFANet(nn.Module):
         d integral straight to the trunk maps and the lat* / bn* parameters on HIP kernels."""
         x = self.normalized(images)
         if torch.is_grad_enabled():
-            return vfa_op.lateral_integrals_train(self.base(x), (self.lat8, self.lat16, self.lat32), (self.bn8, self.bn16, self.bn32))
+            return vfa_op.lateral_integrals_train(self.trunk(x), (self.lat8, self.lat16, self.lat32), (self.bn8, self.bn16, self.bn32))
         parts = ops.lateral_convs([(feat, conv.weight, conv.bias, gn.weight, gn.bias, gn.eps) for feat, conv, gn in
-                                   zip(self.base(x), (self.lat8, self.lat16, self.lat32), (self.bn8, self.bn16, self.bn32))])
+                                   zip(self.trunk(x), (self.lat8, self.lat16, self.lat32), (self.bn8, self.bn16, self.bn32))])
         return ops.integral_images([p[0] for p in parts], [p[1] for p in parts], [p[2] for p in parts], channels_last=True)
 
     def ortho_features(self, images, calibs, grid, distributed=False):
