@@ -959,6 +959,29 @@ int vfa_trunk_conv_f32(const float *x, const long long *x_stride, const void *pa
 int vfa_residual_join_f32(const float *y, const float *a, const float *b, const float *r, const float *ra, const float *rb, int B, int C, int L,
                           int W, float *out, void *stream);
 
+/* ---- the stem of the ResNet trunk at inference (csrc/vfa_stem.hip; the integer rules: csrc/vfa_stem.h) ------------------------------
+ *                         replaces conv1 and the max pooling of resnet.py:100-102, 139-140 in eval mode
+ * float32; fixed summation order and no atomics: the same bits on every run, and an image gives the same bits alone and in a
+ * batch.  Stream-ordered, no host wait, capturable; the workspace is the caller's, the library keeps no state.
+ *
+ * vfa_stem_conv_f32: out (B, O, Lo, Wo) contiguous, Lo = (L - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, every element written: the raw
+ *   convolution F.conv2d(x, weight, stride=2, padding=3) of x (B, 3, L, W), read through its four ELEMENT strides x_stride[4] (>= 0,
+ *   never copied), with weight (O, 3, 7, 7) contiguous, 1 <= O <= 64, without bias.  The exact f32 MFMA: per output ONE fmaf chain
+ *   over k = (c 7 + ky) 7 + kx ascending, a tap outside the image being a zero operand.  workspace: vfa_stem_workspace_bytes(O) bytes,
+ *   16-byte aligned (the weight as the kernel reads it, written by every call).
+ * vfa_stem_pool_f32: out (B, C, (L - 1) / 2 + 1, (W - 1) / 2 + 1) = max_pool2d(max(fmaf(a[b, c], y, b[b, c]), 0), 3, stride 2,
+ *   padding 1) of y (B, C, L, W) contiguous; a, b (B, C) floats (vfa_group_norm_affine_f32 on the raw map: GroupNorm and the ReLU).
+ *   A tap outside the map is skipped; a NaN tap makes its cells NaNs.  Any C >= 1.
+ *
+ * Errors, decided before anything is launched: a negative size, O < 1, C < 1 (the convolution), a NULL required pointer, a negative
+ * element stride, a short or misaligned workspace: VFA_ERR_BAD_ARGUMENT; C != 3 or O > 64 (the convolution;
+ * vfa_stem_workspace_bytes is 0 for such an O), B or L > 65535, L * W >= 2^30: VFA_ERR_UNSUPPORTED.  An empty problem (B == 0 or
+ * L * W == 0; the pooling: C == 0 too) returns 0 and writes nothing. */
+size_t vfa_stem_workspace_bytes(int O);
+int vfa_stem_conv_f32(const float *x, const long long *x_stride, const float *weight, int B, int C, int L, int W, int O, float *out,
+                      void *workspace, size_t workspace_bytes, void *stream);
+int vfa_stem_pool_f32(const float *y, const float *a, const float *b, int B, int C, int L, int W, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,9 @@ SIGNATURES = {
     "vfa_trunk_workspace_bytes": [_c_int],
     "vfa_trunk_conv_f32": [_vp, _vp, _vp, _c_size_t, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_size_t, _vp],
     "vfa_residual_join_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp],
+    "vfa_stem_workspace_bytes": [_c_int],
+    "vfa_stem_conv_f32": [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_size_t, _vp],
+    "vfa_stem_pool_f32": [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp],
 }
 
 _lib = None

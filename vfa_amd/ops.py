@@ -1663,3 +1663,51 @@ def residual_join(y, affine, shortcut, shortcut_affine=None, out=None):
         _launch("vfa_residual_join_f32", _lib.ptr(y), _lib.ptr(a), _lib.ptr(b), _lib.ptr(shortcut), _lib.ptr(ra), _lib.ptr(rb), B, C, L, W,
                 _lib.ptr(out), _lib.current_stream_handle(), tag=(B, C, L, W))
     return out
+
+
+_STEM_MAX_OUT = 64      # kMaxOut of csrc/vfa_stem.h
+
+
+def stem_conv(x, weight):
+    """``F.conv2d(x, weight, stride=2, padding=3)`` for a (O, 3, 7, 7) weight with at most 64 outputs, without bias, at inference on the
+    HIP kernel (``vfa_stem_conv_f32``): the raw map (B, O, (L - 1) // 2 + 1, (W - 1) // 2 + 1) contiguous.  x (B, 3, L, W) float32 is read
+    through its strides (NCHW, channels-last or a slice, never copied).  The exact f32 MFMA: per output one ``fmaf`` chain over
+    k = (c * 7 + ky) * 7 + kx ascending, a tap outside the image being a zero operand -- no scales, no pre-pass: the same bits on
+    every run, alone and in a batch; no host wait, capturable.  Nothing is kept between calls."""
+    stride_arr, (B, C, L, W, O) = _conv_operands("stem_conv", x, weight, kernels=(7,))
+    if C != 3 or O > _STEM_MAX_OUT:
+        raise ValueError(f"stem_conv: weight must be (O, 3, 7, 7) with O <= {_STEM_MAX_OUT}, got {tuple(weight.shape)}")
+    w = weight.detach().contiguous()
+    Lo, Wo = ((L - 1) // 2 + 1, (W - 1) // 2 + 1) if L and W else (0, 0)
+    out = torch.empty((B, O, Lo, Wo), dtype=torch.float32, device=x.device)
+    if out.numel() == 0:
+        return out
+    ws_bytes = _lib.lib().vfa_stem_workspace_bytes(O)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    _launch("vfa_stem_conv_f32", _lib.ptr(x), stride_arr, _lib.ptr(w), B, C, L, W, O, _lib.ptr(out), _lib.ptr(ws), ws_bytes,
+            _lib.current_stream_handle(), tag=(B, C, L, W, O))
+    return out
+
+
+def stem_pool(y, affine):
+    """``F.max_pool2d(relu(a[b, c] * y + b[b, c]), 3, stride=2, padding=1)`` at inference (``vfa_stem_pool_f32``): y (B, C, L, W)
+    contiguous float32, ``affine = (a, b)``, both (B, C) (``group_norm_affine`` on y: GroupNorm and the ReLU applied as the taps are
+    read) -> (B, C, (L - 1) // 2 + 1, (W - 1) // 2 + 1).  Each tap is ``max(fmaf(a, y, b), 0)``, one rounding; taps outside the map are
+    skipped; a NaN reaches exactly the cells whose window holds it."""
+    a, b = affine
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (y, a, b)):
+        raise ValueError("stem_pool: inference only -- an operand requires grad while gradients are enabled (use torch.no_grad())")
+    _lib.require_device(y, a, b)
+    if y.dtype != torch.float32 or y.dim() != 4 or not y.is_contiguous():
+        raise ValueError(f"stem_pool: y must be contiguous float32 (B, C, L, W), got {y.dtype} {tuple(y.shape)}")
+    B, C, L, W = y.shape
+    for t in (a, b):
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, C):
+            raise ValueError(f"stem_pool: the affine is two float32 ({B}, {C}) tensors, got {t.dtype} {tuple(t.shape)}")
+    a, b = a.contiguous(), b.contiguous()
+    Lo, Wo = ((L - 1) // 2 + 1, (W - 1) // 2 + 1) if L and W else (0, 0)
+    out = torch.empty((B, C, Lo, Wo), dtype=torch.float32, device=y.device)
+    if out.numel():
+        _launch("vfa_stem_pool_f32", _lib.ptr(y), _lib.ptr(a), _lib.ptr(b), B, C, L, W, _lib.ptr(out), _lib.current_stream_handle(),
+                tag=(B, C, L, W))
+    return out

@@ -16,8 +16,11 @@ Multi-GPU (``distributed=True``): each rank runs backbone + laterals + projectio
 the HIP kernels of ``csrc/vfa_conv.hip`` from the same parameters (``heads``).
 
 ``trunk_convs="hip"`` (the same kind of attribute; default ``"library"``) runs the residual stages ``layer1`` .. ``layer4`` of the
-ResNet trunk at inference on the HIP kernels of ``csrc/vfa_trunk.hip`` from the same parameters (``trunk``); the stem
-stays the library's.
+ResNet trunk at inference on the HIP kernels of ``csrc/vfa_trunk.hip`` from the same parameters (``trunk``).
+
+``trunk_stem="hip"`` (independent of ``trunk_convs``; default ``"library"``) runs the trunk's stem -- the 7 x 7 stride-2 convolution,
+GroupNorm, ReLU and the max pooling -- at inference on the HIP kernels of ``csrc/vfa_stem.hip`` (``trunk``).  With
+``trunk_stem = trunk_convs = head_convs = "hip"`` no library convolution runs between the camera bytes and the detections.
 """
 import glob
 import os
@@ -46,6 +49,8 @@ PRETRAINED_ENV = "VFA_AMD_PRETRAINED"
 HEAD_CONVS = ("library", "hip")
 # Who runs the residual stages of the trunk (``VFANet.trunk_convs``, ``VFANet.trunk``)
 TRUNK_CONVS = ("library", "hip")
+# Who runs the trunk's stem (``VFANet.trunk_stem``, ``VFANet.trunk``)
+TRUNK_STEM = ("library", "hip")
 
 
 def _find_pretrained(base):
@@ -142,22 +147,38 @@ class _Trunk(nn.Module):
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
 
-    def forward(self, x):
-        x = F.max_pool2d(F.relu(self.bn1(self.conv1(x)), inplace=True), 3, stride=2, padding=1)
+    def stem(self, x):
+        """The 7 x 7 stride-2 convolution, GroupNorm, ReLU and the max pooling (reference resnet.py:139-140) as the library runs them."""
+        return F.max_pool2d(F.relu(self.bn1(self.conv1(x)), inplace=True), 3, stride=2, padding=1)
+
+    def stem_hip(self, x):
+        """``stem`` at inference on ``ops.stem_conv`` / ``ops.group_norm_affine`` / ``ops.stem_pool``: the raw convolution is written
+        once, its GroupNorm is a per (image, channel) affine that the pooling applies with the ReLU as it reads -- the normalised map
+        is never written.  The same function of the same parameters up to the summation order."""
+        y = ops.stem_conv(x, self.conv1.weight)
+        return ops.stem_pool(y, _gn_affine(y, self.bn1))
+
+    def stages(self, x):
+        """``layer1`` .. ``layer4`` on the stem's output -> (f8, f16, f32)."""
         f8 = self.layer2(self.layer1(x))
         f16 = self.layer3(f8)
         return f8, f16, self.layer4(f16)
 
-    def forward_hip(self, x):
-        """``forward`` with the residual stages on the HIP kernels (``_Block.forward_hip``); the stem -- a 7 x 7 stride-2
-        convolution of three channels, GroupNorm, ReLU and the max pooling -- is the library's."""
-        x = F.max_pool2d(F.relu(self.bn1(self.conv1(x)), inplace=True), 3, stride=2, padding=1)
+    def stages_hip(self, x):
+        """``stages`` on the HIP kernels (``_Block.forward_hip``)."""
         maps = []
         for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
             for block in layer:
                 x = block.forward_hip(x)
             maps.append(x)
         return maps[1], maps[2], maps[3]
+
+    def forward(self, x):
+        return self.stages(self.stem(x))
+
+    def forward_hip(self, x):
+        """``forward`` with the residual stages on the HIP kernels; the stem is the library's."""
+        return self.stages_hip(self.stem(x))
 
 
 _DEPTHS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3)}
@@ -178,6 +199,7 @@ class VFANet(nn.Module):
         self.view_reduce = check_view_reduce(view_reduce)
         self.head_convs = "library"  # or "hip" (``heads``); a plain attribute like ``view_reduce``: no ``state_dict`` key
         self.trunk_convs = "library"  # or "hip" (``trunk``); the same kind of attribute
+        self.trunk_stem = "library"  # or "hip" (``trunk``); the same kind of attribute, independent of ``trunk_convs``
         self.input_size = getattr(args, "resize_size", None)  # (H, W) uint8 frames are resized to (train.py:209-214); None: as they are
         self.base = _Trunk(_DEPTHS[base])
         if pretrained:
@@ -211,15 +233,19 @@ class VFANet(nn.Module):
         return (images if images.is_floating_point() else self.mean).new_zeros(0, 256, h, w)
 
     def trunk(self, x):
-        """The normalised images (n,3,iH,iW) -> the trunk's maps (f8, f16, f32), contiguous NCHW float32.  ``trunk_convs``:
-        ``"library"`` is ``self.base(x)``; ``"hip"`` runs ``layer1`` .. ``layer4`` on the kernels of ``csrc/vfa_trunk.hip``
-        (``_Trunk.forward_hip``) where the model is in eval mode, gradients are off and ``x`` is a float32 CUDA tensor with at least
-        one image, and is ``self.base(x)`` anywhere else."""
+        """The normalised images (n,3,iH,iW) -> the trunk's maps (f8, f16, f32), contiguous NCHW float32.  Two independent settings:
+        ``trunk_stem`` names who runs the stem (``"hip"``: the kernels of ``csrc/vfa_stem.hip``, ``_Trunk.stem_hip``) and
+        ``trunk_convs`` who runs ``layer1`` .. ``layer4`` (``"hip"``: the kernels of ``csrc/vfa_trunk.hip``, ``_Trunk.stages_hip``).
+        ``"hip"`` holds where the model is in eval mode, gradients are off and ``x`` is a float32 CUDA tensor with at least one image;
+        anywhere else, and with both settings on ``"library"``, this is ``self.base(x)``."""
         if self.trunk_convs not in TRUNK_CONVS:
             raise ValueError(f"VFANet.trunk: trunk_convs is one of {TRUNK_CONVS}, got {self.trunk_convs!r}")
-        if (self.trunk_convs == "hip" and not self.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
-                and x.dim() == 4 and x.numel() > 0):
-            return self.base.forward_hip(x)
+        if self.trunk_stem not in TRUNK_STEM:
+            raise ValueError(f"VFANet.trunk: trunk_stem is one of {TRUNK_STEM}, got {self.trunk_stem!r}")
+        if ("hip" in (self.trunk_convs, self.trunk_stem) and not self.training and not torch.is_grad_enabled() and x.is_cuda
+                and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0):
+            y = self.base.stem_hip(x) if self.trunk_stem == "hip" else self.base.stem(x)
+            return self.base.stages_hip(y) if self.trunk_convs == "hip" else self.base.stages(y)
         return self.base(x)
 
     def laterals(self, images):
