@@ -926,6 +926,34 @@ size_t vfa_group_norm_workspace_bytes(int B, int groups);
 int vfa_group_norm_affine_f32(const float *x, const long long *x_stride, const float *gamma, const float *beta, float eps, int B, int C,
                               int L, int W, int groups, float *a, float *b, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- training the dense 3x3 convolution above: its two gradients (csrc/vfa_conv_grad.hip; the integer rules: csrc/vfa_conv_grad.h) --
+ *                         replaces the backward of the nn.Conv2d(256, 256, 3) layers of vfanet.py:131-149
+ * y = conv(x, weight) + bias with x (B, C, L, W), weight (O, C, 3, 3), g = dL/dy (B, O, L, W); stride 1, zero padding = dilation,
+ * 1 <= dilation <= 4, float32, C % 32 == 0 and O % 32 == 0.  Fixed summation order and no float atomics: the same bits on every
+ * run.  Stream-ordered, no host wait, capturable; workspaces are the caller's, the library keeps no state.
+ *
+ * vfa_conv3x3_pack_weights_transposed_f32: weight (O, C, 3, 3) contiguous -> the `packed` planes (vfa_conv3x3_packed_bytes(C, O)
+ *   bytes, 16-byte aligned) of w'[c, o, t] = weight[o, c, 8 - t], a convolution with O inputs and C outputs, without a transposed
+ *   copy of the weight: dL/dx = vfa_conv3x3_f32(g, packed', B, C' = O, L, W, O' = C, the same dilation), and a frame's dL/dx is the
+ *   same bits alone and in a batch.
+ * vfa_conv3x3_wgrad_f32: dw[o, c, ty, tx] = sum_b sum_(l, w) g[b, o, l, w] * x[b, c, l + (ty - 1) d, w + (tx - 1) d] ((O, C, 3, 3)
+ *   contiguous, every element written) and, where db is not NULL, db[o] = sum_b sum_(l, w) g[b, o, l, w] (O floats).  g and x are
+ *   read through their four ELEMENT strides (>= 0, never copied).  The product is the three-MFMA fp16 split of csrc/vfa_split.h with
+ *   both operands split as they are staged; each has a power-of-two scale from the absmax of the finite values of EACH frame.  The
+ *   cells are cut into slabs by a rule of (L, W) alone (csrc/vfa_conv_grad.h); one workgroup writes the float32 partial of one
+ *   (frame, slab, tile of 128 outputs x 32 inputs), unscaled by its frame's 2^-(eg + ex); the partials of an element are added in
+ *   ascending (frame, slab) order in float64 and rounded once.  db: per output, float64 sums in a fixed order, rounded once.
+ *   workspace: vfa_conv3x3_wgrad_workspace_bytes(B, O, C, L, W) bytes, 16-byte aligned.
+ *
+ * Errors, decided before anything is launched: a negative size, O < 1, C < 1, dilation < 1, a NULL required pointer, a negative
+ * stride, a short or misaligned workspace, a `packed` of another size: VFA_ERR_BAD_ARGUMENT; C % 32 != 0, O % 32 != 0, dilation >
+ * 4, B or L > 65535, L * W >= 2^30, O * C * 9 >= 2^30: VFA_ERR_UNSUPPORTED (vfa_conv3x3_wgrad_workspace_bytes is 0 for such sizes
+ * and for an empty problem).  B == 0 or L * W == 0: dw and db are zeros (the empty sum). */
+int vfa_conv3x3_pack_weights_transposed_f32(const float *weight, int O, int C, void *packed, size_t packed_bytes, void *stream);
+size_t vfa_conv3x3_wgrad_workspace_bytes(int B, int O, int C, int L, int W);
+int vfa_conv3x3_wgrad_f32(const float *g, const long long *g_stride, const float *x, const long long *x_stride, int B, int C, int L, int W,
+                          int O, int dilation, float *dw, float *db, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- the residual stages of the ResNet trunk at inference (csrc/vfa_trunk.hip; the integer rules: csrc/vfa_trunk.h) ----------------
  *                         replaces the nn.Conv2d / GroupNorm / ReLU calls of a block, resnet.py:26-57, in eval mode
  * The dense kernel above with a stride, one or nine taps and a prologue; float32; x (B, C, L, W) is read through its four ELEMENT

@@ -149,6 +149,9 @@ SIGNATURES = {
     "vfa_conv3x3_few_f32": [_vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp],
     "vfa_group_norm_workspace_bytes": [_c_int, _c_int],
     "vfa_group_norm_affine_f32": [_vp, _vp, _vp, _vp, _c_float, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_size_t, _vp],
+    "vfa_conv3x3_pack_weights_transposed_f32": [_vp, _c_int, _c_int, _vp, _c_size_t, _vp],
+    "vfa_conv3x3_wgrad_workspace_bytes": [_c_int, _c_int, _c_int, _c_int, _c_int],
+    "vfa_conv3x3_wgrad_f32": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_size_t, _vp],
     "vfa_trunk_packed_bytes": [_c_int, _c_int, _c_int],
     "vfa_trunk_pack_weights_f32": [_vp, _c_int, _c_int, _c_int, _vp, _c_size_t, _vp],
     "vfa_trunk_workspace_bytes": [_c_int],

@@ -68,5 +68,10 @@ VFA_CONV_HD size_t packed_index(int o, int c, int t, int piece, int C)
     return slice * kSliceHalves + (size_t)(((piece * 4 + cc / 8) * kTileOut + o % kTileOut) * 8 + cc % 8);
 }
 
+// host side, defined in vfa_conv.hip: per frame b the maximum of the bit patterns of the finite |x[b]| into absmax[b] (merged with an
+// integer atomicMax: the caller zeroes absmax[0 .. B - 1] on the stream first) -- the operand's power-of-two scale of vfa_split.h.
+// x (B, C, L, W) is read through its four element strides.  0, or the error of the entry points (an empty map launches nothing).
+int frame_absmax(const float *x, const long long *stride, int B, int C, int L, int W, unsigned *absmax, void *stream);
+
 } // namespace vfa_conv
 #endif // VFA_CONV_H

@@ -5,7 +5,9 @@
 //
 //   1. conv_absmax_kernel: per frame (and once per weight) the maximum of the bit patterns of the finite values, merged with an
 //      integer atomicMax per block -- the operand's power-of-two scale of the fp16 split (vfa_split.h).
-//   2. conv_pack_kernel: the weight (O, C, 3, 3) scaled and split into the packed hi / lo fp16 planes of vfa_conv.h, once per weight.
+//   2. conv_pack_kernel: the weight (O, C, 3, 3) scaled and split into the packed hi / lo fp16 planes of vfa_conv.h, once per weight;
+//      or the planes of its transposed, tap-mirrored form, with which this file's dense kernel gives the input gradient
+//      (vfa_conv_grad.hip has the weight gradient).
 //   3. conv_dense_kernel<D>: an implicit GEMM with M = outputs, N = cells, K = 9 C.  A workgroup of 4 waves owns a tile of 4 map rows x
 //      32 columns and 128 outputs; wave (wm, wn) takes the rows 2 wm, 2 wm + 1 and the outputs 64 wn .. 64 wn + 63: four 32 x 32
 //      accumulators.  K runs in chunks of 32 channels: the tile's window (the tile grown by the dilation) of the chunk is loaded
@@ -85,8 +87,10 @@ __global__ __launch_bounds__(kThreads) void conv_absmax_kernel(const Map m, unsi
     }
 }
 
-// one thread per four channels of one (output, tap): both pieces
-__global__ __launch_bounds__(kThreads) void conv_pack_kernel(const float *__restrict__ weight, int O, int C, unsigned char *__restrict__ packed)
+// one thread per four channels of one (output, tap): both pieces.  transposed: `weight` is (C, O, 3, 3) and the planes are those of
+// its transposed, tap-mirrored form w'[o, c, t] = weight[c, o, 8 - t], the weight of the convolution's input gradient
+__global__ __launch_bounds__(kThreads) void conv_pack_kernel(const float *__restrict__ weight, int O, int C, int transposed,
+                                                             unsigned char *__restrict__ packed)
 {
     const size_t per_piece = packed_halves(O, C) / 8; // quads of one piece: a thread writes its hi quad and its lo quad
     const size_t q = (size_t)blockIdx.x * kThreads + threadIdx.x;
@@ -105,7 +109,8 @@ __global__ __launch_bounds__(kThreads) void conv_pack_kernel(const float *__rest
     float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (o < O) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = weight[((size_t)o * C + c + j) * kTaps + t] * sw;
+        for (int j = 0; j < 4; ++j)
+            v[j] = (transposed ? weight[((size_t)(c + j) * O + o) * kTaps + (kTaps - 1 - t)] : weight[((size_t)o * C + c + j) * kTaps + t]) * sw;
     }
     uint2 hi, lo;
     vfa_dev::fp16_saturate_mode(true);
@@ -420,17 +425,7 @@ int launch_dense(const Map &m, const unsigned *absmax, const unsigned char *pack
     return (int)hipGetLastError();
 }
 
-} // namespace
-
-extern "C" {
-
-size_t vfa_conv3x3_packed_bytes(int O, int C)
-{
-    if (O < 1 || C < 1 || C % kChunkC != 0 || (long long)O * C * kTaps > INT32_MAX / 2) return 0;
-    return kPackHeaderBytes + packed_halves(O, C) * 2;
-}
-
-int vfa_conv3x3_pack_weights_f32(const float *weight, int O, int C, void *packed, size_t packed_bytes, void *stream)
+int pack_weights(const float *weight, int O, int C, int transposed, void *packed, size_t packed_bytes, void *stream)
 {
     if (O < 1 || C < 1 || !weight || !packed) return VFA_ERR_BAD_ARGUMENT;
     const size_t need = vfa_conv3x3_packed_bytes(O, C);
@@ -442,9 +437,38 @@ int vfa_conv3x3_pack_weights_f32(const float *weight, int O, int C, void *packed
     Map m = {weight, 0, 0, 0, 1, 1, 1, 1, O * C * kTaps};
     hipLaunchKernelGGL(conv_absmax_kernel, absmax_grid(m), dim3(kThreads), 0, s, m, (unsigned *)packed);
     const size_t quads = packed_halves(O, C) / 8;
-    hipLaunchKernelGGL(conv_pack_kernel, dim3((unsigned)((quads + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, weight, O, C,
+    hipLaunchKernelGGL(conv_pack_kernel, dim3((unsigned)((quads + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, weight, O, C, transposed,
                        (unsigned char *)packed);
     return (int)hipGetLastError();
+}
+
+} // namespace
+
+int vfa_conv::frame_absmax(const float *x, const long long *stride, int B, int C, int L, int W, unsigned *absmax, void *stream)
+{
+    Map m = {};
+    const int status = check_map(x, stride, B, C, L, W, m);
+    if (status != 0) return status == 1 ? 0 : status;
+    hipLaunchKernelGGL(conv_absmax_kernel, absmax_grid(m), dim3(kThreads), 0, (hipStream_t)stream, m, absmax);
+    return (int)hipGetLastError();
+}
+
+extern "C" {
+
+size_t vfa_conv3x3_packed_bytes(int O, int C)
+{
+    if (O < 1 || C < 1 || C % kChunkC != 0 || (long long)O * C * kTaps > INT32_MAX / 2) return 0;
+    return kPackHeaderBytes + packed_halves(O, C) * 2;
+}
+
+int vfa_conv3x3_pack_weights_f32(const float *weight, int O, int C, void *packed, size_t packed_bytes, void *stream)
+{
+    return pack_weights(weight, O, C, 0, packed, packed_bytes, stream);
+}
+
+int vfa_conv3x3_pack_weights_transposed_f32(const float *weight, int O, int C, void *packed, size_t packed_bytes, void *stream)
+{
+    return pack_weights(weight, C, O, 1, packed, packed_bytes, stream); // the planes of a convolution with O inputs and C outputs
 }
 
 size_t vfa_conv3x3_workspace_bytes(int B)

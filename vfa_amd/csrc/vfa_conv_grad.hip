@@ -1,0 +1,329 @@
+// vfa_conv_grad.hip -- the weight gradient of the dense 3x3 convolution of vfa_conv.hip (stride 1, zero padding = dilation, dilation
+// 1..4), for training the 256 -> 256 layers of the BEV heads:
+//
+//     dW[o, c, ty, tx] = sum_b sum_(l, w) g[b, o, l, w] x[b, c, l + (ty - 1) d, w + (tx - 1) d]        db[o] = sum_b sum_(l, w) g[b, o, l, w]
+//
+// g (B, O, L, W) and x (B, C, L, W) float32, both read through their four element strides; dW (O, C, 3, 3) contiguous.  Fixed summation
+// order, no float atomics: the same bits on every run.  (The input gradient is the forward kernel on g with the transposed,
+// tap-mirrored weight: vfa_conv3x3_pack_weights_transposed_f32.)  The integer rules: vfa_conv_grad.h.
+//
+//   1. conv_absmax_kernel of vfa_conv.hip on g and on x: per frame the power-of-two scale of the fp16 split (vfa_split.h).
+//   2. wgrad_kernel<D>: an implicit GEMM with M = outputs, N = inputs, K = cells, once per tap.  A workgroup of 4 waves owns one
+//      (frame, slab of cells) and a tile of 128 outputs x 32 inputs x 9 taps; wave w takes the outputs 32 w .. 32 w + 31: nine 32 x 32
+//      accumulators.  K runs in the forward kernel's tiles of 4 map rows x 32 columns: the tile's cells of g (128 outputs) and the
+//      tile's window of x (the tile grown by the dilation, 32 inputs) are loaded through the strides, scaled, split under
+//      MODE.FP16_OVFL and kept in LDS as two fp16 planes each, [cell][channel]; the next tile is in flight under the products.  Both
+//      MFMA operands want 8 consecutive k of ONE channel per lane, which in these planes is a column: ds_read_b64_tr_b16, the
+//      transposed LDS read, delivers it.  A tap moves the window location of a cell, never the alignment of a read, so the nine
+//      taps read the one window at nine offsets.  A product is the three v_mfma_f32_32x32x16_f16 of vfa_split.h (g_lo x_hi, g_hi x_hi,
+//      g_hi x_lo).  Epilogue: the partial acc 2^-(eg + ex) of the frame's two scales to the workspace, [frame][slab][tap][o][c].
+//   3. wgrad_merge_kernel: per element of dW the partials in ascending (frame, slab) order, summed in float64, rounded once.
+//   4. bias_grad_kernel: per output a workgroup; thread i sums the cells i, i + 256, .. of frame 0, then of frame 1, .. in float64,
+//      the 256 sums are merged in a fixed tree and rounded once.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "vfa_conv.h"
+#include "vfa_conv_grad.h"
+#include "vfa_hip.h"
+#include "vfa_split.h"
+
+namespace {
+
+using namespace vfa_conv;
+using namespace vfa_conv_grad;
+using vfa_dev::f16x4;
+using vfa_dev::f16x8;
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
+
+constexpr int kThreads = 256;
+constexpr int kExp = 14;  // both operands are scaled into [2^14, 2^15): a product is below 2^30 and a slab's sum far inside fp32
+constexpr int kTileCells = kTileRows * kTileCols;
+constexpr int kGQuads = kTileCells * (kTileO / 4);
+constexpr int kGLoads = kGQuads / kThreads;
+constexpr int kGPlaneHalves = kTileCells * kGHalves;
+
+struct Map {
+    const float *x;
+    long long s_frame, s_chan, s_row, s_col; // element strides, >= 0
+};
+
+template <int D> struct Grad {
+    static constexpr int kLoc = (kTileRows + 2 * D) * (kTileCols + 2 * D);
+    static constexpr int kQuads = kLoc * (kTileC / 4);
+    static constexpr int kLoads = (kQuads + kThreads - 1) / kThreads;
+    static constexpr int kPlaneHalves = kLoc * kLocHalves;
+    static constexpr int kLdsBytes = (2 * kPlaneHalves + 2 * kGPlaneHalves) * 2;
+};
+
+// quad e of the window of x: (location, four inputs 4 c4 .. 4 c4 + 3), consecutive threads on consecutive addresses of the map
+template <int D> __device__ __forceinline__ void x_quad_of(int e, bool chan_fast, int &loc, int &c4)
+{
+    if (chan_fast) { c4 = e & 7; loc = e >> 3; }
+    else { c4 = e / Grad<D>::kLoc; loc = e - c4 * Grad<D>::kLoc; }
+}
+// quad e of the tile of g: (cell of the tile, four outputs)
+__device__ __forceinline__ void g_quad_of(int e, bool chan_fast, int &cell, int &c4)
+{
+    if (chan_fast) { c4 = e & (kTileO / 4 - 1); cell = e / (kTileO / 4); }
+    else { c4 = e / kTileCells; cell = e & (kTileCells - 1); }
+}
+
+template <int D>
+__device__ __forceinline__ void x_load(const Map m, int L, int W, int b, int y0, int x0, int c0, bool chan_fast, int tid, float (&v)[Grad<D>::kLoads][4])
+{
+#pragma unroll
+    for (int j = 0; j < Grad<D>::kLoads; ++j) {
+        const int e = tid + kThreads * j;
+        int loc, c4, y, x;
+        x_quad_of<D>(e, chan_fast, loc, c4);
+        const bool ok = e < Grad<D>::kQuads && window_position(loc, y0, x0, D, L, W, y, x);
+        const float *p = m.x + (ok ? b * m.s_frame + (long long)(c0 + 4 * c4) * m.s_chan + y * m.s_row + x * m.s_col : 0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[j][k] = ok ? p[k * m.s_chan] : 0.0f;
+    }
+}
+
+template <int D>
+__device__ __forceinline__ void x_store(_Float16 *x_hi, _Float16 *x_lo, float sx, bool chan_fast, int tid, const float (&v)[Grad<D>::kLoads][4])
+{
+#pragma unroll
+    for (int j = 0; j < Grad<D>::kLoads; ++j) {
+        const int e = tid + kThreads * j;
+        int loc, c4;
+        x_quad_of<D>(e, chan_fast, loc, c4);
+        uint2 hi, lo;
+        vfa_dev::split_f16x4(v[j][0] * sx, v[j][1] * sx, v[j][2] * sx, v[j][3] * sx, hi, lo);
+        if (e < Grad<D>::kQuads) {
+            *(uint2 *)(x_hi + loc * kLocHalves + 4 * c4) = hi;
+            *(uint2 *)(x_lo + loc * kLocHalves + 4 * c4) = lo;
+        }
+    }
+}
+
+// the tile's cells of g: outputs o0 .. o0 + 127; a cell outside the map and an output past O are zeros
+__device__ __forceinline__ void g_load(const Map m, int L, int W, int O, int b, int y0, int x0, int o0, bool chan_fast, int tid, float (&v)[kGLoads][4])
+{
+#pragma unroll
+    for (int j = 0; j < kGLoads; ++j) {
+        int cell, c4;
+        g_quad_of(tid + kThreads * j, chan_fast, cell, c4);
+        const int y = y0 + cell / kTileCols, x = x0 + cell % kTileCols, o = o0 + 4 * c4;
+        const bool ok = y < L && x < W && o < O; // (O % 4 == 0: a quad is inside or outside)
+        const float *p = m.x + (ok ? b * m.s_frame + (long long)o * m.s_chan + y * m.s_row + x * m.s_col : 0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[j][k] = ok ? p[k * m.s_chan] : 0.0f;
+    }
+}
+
+__device__ __forceinline__ void g_store(_Float16 *g_hi, _Float16 *g_lo, float sg, bool chan_fast, int tid, const float (&v)[kGLoads][4])
+{
+#pragma unroll
+    for (int j = 0; j < kGLoads; ++j) {
+        int cell, c4;
+        g_quad_of(tid + kThreads * j, chan_fast, cell, c4);
+        uint2 hi, lo;
+        vfa_dev::split_f16x4(v[j][0] * sg, v[j][1] * sg, v[j][2] * sg, v[j][3] * sg, hi, lo);
+        *(uint2 *)(g_hi + cell * kGHalves + 4 * c4) = hi;
+        *(uint2 *)(g_lo + cell * kGHalves + 4 * c4) = lo;
+    }
+}
+
+// ds_read_b64_tr_b16: per group of 16 lanes a block of 4 rows x 16 columns of the [cell][channel] plane, column-major -- lane 4 q + p of
+// the group gives the address of row q, columns 4 p .. 4 p + 3 (8-byte aligned), lane i receives column i, row q in element q.
+// Every lane of the wave must be active.
+__device__ __forceinline__ f16x4 read_transposed(const _Float16 *p)
+{
+    return __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)p));
+}
+// the 32x32x16 operand of 32 channels x 16 cells: `p` is this lane's address in the first of its 8 cells, `step` the halves between
+// two cells; element j of the lane is cell 8 h + j of the step (h = lane >> 5), its channel lane & 31
+__device__ __forceinline__ f16x8 operand(const _Float16 *p, int step)
+{
+    const f16x4 a = read_transposed(p), b = read_transposed(p + 4 * step);
+    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+template <int D>
+__global__ __launch_bounds__(kThreads) void wgrad_kernel(const Map mg, const Map mx, const unsigned *__restrict__ absmax, int B, int C, int L, int W,
+                                                         int O, float *__restrict__ partial)
+{
+    extern __shared__ __align__(16) unsigned char lds[];
+    _Float16 *x_hi = (_Float16 *)lds, *x_lo = x_hi + Grad<D>::kPlaneHalves, *g_hi = x_lo + Grad<D>::kPlaneHalves, *g_lo = g_hi + kGPlaneHalves;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int slab = blockIdx.x, b = blockIdx.z, n_c = C / kTileC;
+    const int o0 = ((int)blockIdx.y / n_c) * kTileO, c0 = ((int)blockIdx.y % n_c) * kTileC;
+    const bool g_fast = mg.s_chan == 1, x_fast = mx.s_chan == 1;
+    const int eg = vfa_dev::split_exponent(absmax[b], kExp), ex = vfa_dev::split_exponent(absmax[B + b], kExp);
+    const float sg = vfa_dev::pow2f(eg), sx = vfa_dev::pow2f(ex);
+    const int tile_begin = slab_begin(slab, L, W), tile_end = slab_begin(slab + 1, L, W);
+
+    // this lane's part of the transposed reads: row q of its group's block is cell 8 h + q of the step, columns 4 p .. of the
+    // group's 16 channels
+    const int q = (lane >> 2) & 3, p = lane & 3, half16 = (lane >> 4) & 1;
+    const int k_lane = 8 * h + q, ch_lane = 16 * half16 + 4 * p;
+
+    float vx[Grad<D>::kLoads][4], vg[kGLoads][4];
+    int y0, x0;
+    tile_origin(tile_begin, W, y0, x0);
+    x_load<D>(mx, L, W, b, y0, x0, c0, x_fast, tid, vx);
+    g_load(mg, L, W, O, b, y0, x0, o0, g_fast, tid, vg);
+    vfa_dev::fp16_saturate_mode(true);
+    x_store<D>(x_hi, x_lo, sx, x_fast, tid, vx);
+    g_store(g_hi, g_lo, sg, g_fast, tid, vg);
+    vfa_dev::fp16_saturate_mode(false);
+    __syncthreads();
+
+    f32x16 acc[kTaps];
+#pragma unroll
+    for (int t = 0; t < kTaps; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+
+    for (int tile = tile_begin; tile < tile_end; ++tile) {
+        const bool more = tile + 1 < tile_end; // (uniform)
+        if (more) {
+            tile_origin(tile + 1, W, y0, x0);
+            x_load<D>(mx, L, W, b, y0, x0, c0, x_fast, tid, vx);
+            g_load(mg, L, W, O, b, y0, x0, o0, g_fast, tid, vg);
+        }
+#pragma unroll 1
+        for (int ks = 0; ks < kTileCells / 16; ++ks) { // 16 cells of one tile row
+            const int ry = ks >> 1, rx = (ks & 1) * 16 + k_lane;
+            const int g_at = (ry * kTileCols + rx) * kGHalves + wave * 32 + ch_lane;
+            const f16x8 gh = operand(g_hi + g_at, kGHalves), gl = operand(g_lo + g_at, kGHalves);
+#pragma unroll
+            for (int t = 0; t < kTaps; ++t) {
+                const int x_at = window_index(ry, rx, t, D) * kLocHalves + ch_lane;
+                const f16x8 xh = operand(x_hi + x_at, kLocHalves), xl = operand(x_lo + x_at, kLocHalves);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gl, xh, acc[t], 0, 0, 0); // rows = outputs, columns = inputs
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gh, xh, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gh, xl, acc[t], 0, 0, 0);
+            }
+        }
+        __syncthreads(); // the planes are free
+        if (more) {
+            vfa_dev::fp16_saturate_mode(true);
+            x_store<D>(x_hi, x_lo, sx, x_fast, tid, vx);
+            g_store(g_hi, g_lo, sg, g_fast, tid, vg);
+            vfa_dev::fp16_saturate_mode(false);
+            __syncthreads();
+        }
+    }
+
+    const float inv = vfa_dev::pow2f(-(eg + ex));
+    const int c = c0 + r;
+#pragma unroll
+    for (int t = 0; t < kTaps; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { // C/D: column = lane & 31, row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5)
+            const int o = o0 + wave * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+            if (o < O) partial[partial_index(b, slab, t, o, c, O, C, L, W)] = acc[t][i] * inv;
+        }
+}
+
+// one thread per element (t, o, c) of a partial: consecutive threads on consecutive addresses of every partial
+__global__ __launch_bounds__(kThreads) void wgrad_merge_kernel(const float *__restrict__ partial, int n_partials, int O, int C, float *__restrict__ dw)
+{
+    const size_t per = partial_floats(O, C), i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= per) return;
+    double sum = 0.0;
+    for (int k = 0; k < n_partials; ++k) sum += (double)partial[(size_t)k * per + i]; // ascending (frame, slab)
+    const size_t oc = i % ((size_t)O * C), t = i / ((size_t)O * C);
+    dw[oc * kTaps + t] = (float)sum;
+}
+
+// grid (O): thread i takes the cells i, i + 256, .. of frame 0, then of frame 1, ..
+__global__ __launch_bounds__(kThreads) void bias_grad_kernel(const Map mg, int B, int L, int W, float *__restrict__ db)
+{
+    __shared__ double red[kThreads];
+    const int tid = threadIdx.x, o = blockIdx.x, plane = L * W;
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const float *src = mg.x + b * mg.s_frame + (long long)o * mg.s_chan;
+        for (int i = tid; i < plane; i += kThreads) {
+            const int y = i / W, x = i - y * W;
+            s += (double)src[y * mg.s_row + x * mg.s_col];
+        }
+    }
+    red[tid] = s;
+    __syncthreads();
+    for (int st = kThreads / 2; st > 0; st >>= 1) { // a fixed tree
+        if (tid < st) red[tid] += red[tid + st];
+        __syncthreads();
+    }
+    if (tid == 0) db[o] = (float)red[0];
+}
+
+size_t scales_bytes(int B) { return ((size_t)2 * B * sizeof(unsigned) + 255) / 256 * 256; }
+
+template <int D>
+int launch_wgrad(const Map &mg, const Map &mx, const unsigned *absmax, int B, int C, int L, int W, int O, float *partial, hipStream_t s)
+{
+    static bool attr_set = false; // idempotent: a race only repeats the call
+    if (!attr_set) {
+        const hipError_t e = hipFuncSetAttribute((const void *)wgrad_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, Grad<D>::kLdsBytes);
+        if (e != hipSuccess) return (int)e;
+        attr_set = true;
+    }
+    const dim3 grid((unsigned)slabs(L, W), (unsigned)(((O + kTileO - 1) / kTileO) * (C / kTileC)), (unsigned)B);
+    hipLaunchKernelGGL(wgrad_kernel<D>, grid, dim3(kThreads), Grad<D>::kLdsBytes, s, mg, mx, absmax, B, C, L, W, O, partial);
+    return (int)hipGetLastError();
+}
+
+bool sizes_ok(int B, int O, int C, int L, int W)
+{
+    return B <= 65535 && L <= 65535 && (long long)L * W <= INT32_MAX / 2 && (long long)O * C * kTaps <= INT32_MAX / 2 &&
+           (long long)((O + kTileO - 1) / kTileO) * (C / kTileC) <= 65535;
+}
+
+} // namespace
+
+extern "C" {
+
+size_t vfa_conv3x3_wgrad_workspace_bytes(int B, int O, int C, int L, int W)
+{
+    if (B <= 0 || O < 1 || C < 1 || L <= 0 || W <= 0 || O % 32 != 0 || C % kTileC != 0 || !sizes_ok(B, O, C, L, W)) return 0;
+    return scales_bytes(B) + (size_t)B * slabs(L, W) * partial_floats(O, C) * sizeof(float);
+}
+
+int vfa_conv3x3_wgrad_f32(const float *g, const long long *g_stride, const float *x, const long long *x_stride, int B, int C, int L, int W,
+                          int O, int dilation, float *dw, float *db, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (B < 0 || C < 1 || L < 0 || W < 0 || O < 1 || dilation < 1 || !dw) return VFA_ERR_BAD_ARGUMENT;
+    if (O % 32 != 0 || C % kTileC != 0 || dilation > kMaxDilation || !sizes_ok(B, O, C, L, W)) return VFA_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    if (B == 0 || (long long)L * W == 0) { // an empty sum
+        hipError_t e = hipMemsetAsync(dw, 0, (size_t)O * C * kTaps * sizeof(float), s);
+        if (e == hipSuccess && db) e = hipMemsetAsync(db, 0, (size_t)O * sizeof(float), s);
+        return (int)e;
+    }
+    if (!g || !g_stride || !x || !x_stride) return VFA_ERR_BAD_ARGUMENT;
+    for (int i = 0; i < 4; ++i)
+        if (g_stride[i] < 0 || x_stride[i] < 0) return VFA_ERR_BAD_ARGUMENT;
+    if (!workspace || ((uintptr_t)workspace & 15) != 0 || workspace_bytes < vfa_conv3x3_wgrad_workspace_bytes(B, O, C, L, W))
+        return VFA_ERR_BAD_ARGUMENT;
+    const Map mg = {g, g_stride[0], g_stride[1], g_stride[2], g_stride[3]}, mx = {x, x_stride[0], x_stride[1], x_stride[2], x_stride[3]};
+    unsigned *absmax = (unsigned *)workspace;
+    float *partial = (float *)((unsigned char *)workspace + scales_bytes(B));
+    const hipError_t e = hipMemsetAsync(absmax, 0, scales_bytes(B), s);
+    if (e != hipSuccess) return (int)e;
+    int status = vfa_conv::frame_absmax(g, g_stride, B, O, L, W, absmax, stream);
+    if (status == 0) status = vfa_conv::frame_absmax(x, x_stride, B, C, L, W, absmax + B, stream);
+    if (status != 0) return status;
+    switch (dilation) {
+    case 1: status = launch_wgrad<1>(mg, mx, absmax, B, C, L, W, O, partial, s); break;
+    case 2: status = launch_wgrad<2>(mg, mx, absmax, B, C, L, W, O, partial, s); break;
+    case 3: status = launch_wgrad<3>(mg, mx, absmax, B, C, L, W, O, partial, s); break;
+    default: status = launch_wgrad<4>(mg, mx, absmax, B, C, L, W, O, partial, s); break;
+    }
+    if (status != 0) return status;
+    const size_t per = partial_floats(O, C);
+    hipLaunchKernelGGL(wgrad_merge_kernel, dim3((unsigned)((per + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, partial, B * slabs(L, W), O, C, dw);
+    if (db) hipLaunchKernelGGL(bias_grad_kernel, dim3((unsigned)O), dim3(kThreads), 0, s, mg, B, L, W, db);
+    return (int)hipGetLastError();
+}
+
+} // extern "C"

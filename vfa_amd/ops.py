@@ -1,4 +1,4 @@
-"""Functional wrappers, one per entry point of ``include/vfa_hip.h`` (no autograd, no fallback).
+"""Functional wrappers, one per entry point of ``include/vfa_hip.h`` (no fallback; no autograd but for ``conv3x3_train``).
 
 Tensors are device tensors; every call is asynchronous on the current torch HIP stream.
 """
@@ -1468,9 +1468,10 @@ def _conv_kept(kind, operands, extra, dev, make):
     return kept.tensors
 
 
-def _conv_operands(name, x, weight, *more, kernels=(3,)):
-    """What the dense convolutions share: device float32 operands, inference only -> (stride array, (B, C, L, W, O))."""
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, *more)):
+def _conv_operands(name, x, weight, *more, kernels=(3,), inference=True):
+    """What the dense convolutions share: device float32 operands, inference only (but for ``conv3x3_train``) -> (stride array,
+    (B, C, L, W, O))."""
+    if inference and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, *more)):
         raise ValueError(f"{name}: inference only -- an operand requires grad while gradients are enabled (use torch.no_grad())")
     _lib.require_device(x, weight, *more)
     if x.dtype != torch.float32 or x.dim() != 4:
@@ -1484,19 +1485,26 @@ def _conv_operands(name, x, weight, *more, kernels=(3,)):
     return (ctypes.c_longlong * 4)(*x.stride()), (B, C, L, W, weight.shape[0])
 
 
+def _conv3x3_pack(weight, transposed=False):
+    """One launch of ``vfa_conv3x3_pack_weights_f32``, or of ``vfa_conv3x3_pack_weights_transposed_f32`` (the planes of the
+    transposed, tap-mirrored weight: the convolution that gives the input gradient) -> (packed, bytes), kept nowhere."""
+    O, C = int(weight.shape[0]), int(weight.shape[1])
+    nbytes = _lib.lib().vfa_conv3x3_packed_bytes(C, O) if transposed else _lib.lib().vfa_conv3x3_packed_bytes(O, C)
+    if nbytes == 0:
+        raise ValueError(f"conv3x3: {'O' if transposed else 'C'} must be a multiple of 32, got weight {tuple(weight.shape)}")
+    w = weight.detach().contiguous()
+    packed = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+    _launch("vfa_conv3x3_pack_weights_transposed_f32" if transposed else "vfa_conv3x3_pack_weights_f32", _lib.ptr(w), O, C, _lib.ptr(packed),
+            nbytes, _lib.current_stream_handle(), tag=(O, C))
+    return packed, nbytes
+
+
 def conv3x3_packed_weight(weight):
     """The pre-split fp16 planes of a (O, C, 3, 3) weight (``vfa_conv3x3_pack_weights_f32``), kept by the weight's identity and version."""
-    O, C = int(weight.shape[0]), int(weight.shape[1])
-    nbytes = _lib.lib().vfa_conv3x3_packed_bytes(O, C)
-    if nbytes == 0:
+    if _lib.lib().vfa_conv3x3_packed_bytes(int(weight.shape[0]), int(weight.shape[1])) == 0:
         raise ValueError(f"conv3x3: C must be a multiple of 32, got weight {tuple(weight.shape)}")
-
-    def make():
-        w = weight.detach().contiguous()
-        packed = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-        _launch("vfa_conv3x3_pack_weights_f32", _lib.ptr(w), O, C, _lib.ptr(packed), nbytes, _lib.current_stream_handle(), tag=(O, C))
-        return (packed,)
-    return _conv_kept("pack", (weight,), None, weight.device, make)[0], nbytes
+    packed = _conv_kept("pack", (weight,), None, weight.device, lambda: _conv3x3_pack(weight)[:1])[0]
+    return packed, packed.numel()
 
 
 def bn_fold(bn_weight, bn_bias, running_mean, running_var, eps, bias=None):
@@ -1533,6 +1541,12 @@ def conv3x3(x, weight, dilation=1, scale=None, shift=None, relu=False):
         if t is not None and t.numel() != O:
             raise ValueError(f"conv3x3: {name} must have {O} values, got {tuple(t.shape)}")
     packed, nbytes = conv3x3_packed_weight(weight)
+    return _conv3x3_launch(x, stride, packed, nbytes, scale, shift, relu, (B, C, L, W, O), dilation)
+
+
+def _conv3x3_launch(x, stride, packed, nbytes, scale, shift, relu, sizes, dilation):
+    """``vfa_conv3x3_f32`` on checked operands and a packed weight -> (B, O, L, W) contiguous."""
+    B, C, L, W, O = sizes
     scale = None if scale is None else scale.detach().contiguous()
     shift = None if shift is None else shift.detach().contiguous()
     out = torch.empty((B, O, L, W), dtype=torch.float32, device=x.device)
@@ -1543,6 +1557,79 @@ def conv3x3(x, weight, dilation=1, scale=None, shift=None, relu=False):
     _launch("vfa_conv3x3_f32", _lib.ptr(x), stride, _lib.ptr(packed), nbytes, _lib.ptr(scale), _lib.ptr(shift), int(bool(relu)), B, C, L, W,
             O, int(dilation), _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(), tag=(B, C, L, W, O, int(dilation)))
     return out
+
+
+def conv3x3_input_grad(grad, weight, dilation=1):
+    """dL/dx of ``y = F.conv2d(x, weight, padding=dilation, dilation=dilation)`` from grad = dL/dy (B, O, L, W), read through its
+    strides: the forward kernel on ``grad`` with the transposed, tap-mirrored weight, packed from ``weight`` (O, C, 3, 3) as it lies
+    (``vfa_conv3x3_pack_weights_transposed_f32``) -> (B, C, L, W) contiguous; a frame gives the same bits alone and in a batch."""
+    O, C = int(weight.shape[0]), int(weight.shape[1])
+    B, _, L, W = grad.shape
+    packed, nbytes = _conv3x3_pack(weight, transposed=True)
+    return _conv3x3_launch(grad, (ctypes.c_longlong * 4)(*grad.stride()), packed, nbytes, None, None, False, (B, O, L, W, C), dilation)
+
+
+def conv3x3_weight_grad(grad, x, dilation=1, want_bias=False, want_partials=False):
+    """dL/dweight (O, C, 3, 3), and dL/dbias (O) or None, of ``y = F.conv2d(x, weight, bias, padding=dilation, dilation=dilation)``
+    from grad = dL/dy (B, O, L, W) and x (B, C, L, W), both read through their strides (``vfa_conv3x3_wgrad_f32``): the three-product
+    fp16 split with per-frame power-of-two scales of both operands, slab partials merged in ascending (frame, slab) order in
+    float64 -- no float atomics, the same bits on every run.  ``want_partials``: a third result, the float32 partials the merge read,
+    (B, slabs, 9, O, C) (a view of the call's workspace; for tests of the merge order)."""
+    B, C, L, W = x.shape
+    O = int(grad.shape[1])
+    dw = torch.empty((O, C, 3, 3), dtype=torch.float32, device=x.device)
+    db = torch.empty(O, dtype=torch.float32, device=x.device) if want_bias else None
+    ws_bytes = _lib.lib().vfa_conv3x3_wgrad_workspace_bytes(B, O, C, L, W)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+    _launch("vfa_conv3x3_wgrad_f32", _lib.ptr(grad), (ctypes.c_longlong * 4)(*grad.stride()), _lib.ptr(x), (ctypes.c_longlong * 4)(*x.stride()),
+            B, C, L, W, O, int(dilation), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(),
+            tag=(B, C, L, W, O, int(dilation)))
+    if want_partials:
+        head = (2 * B * 4 + 255) // 256 * 256   # the two scales of every frame, padded
+        return dw, db, ws[head:ws_bytes].view(torch.float32).view(B, -1, 9, O, C)
+    return dw, db
+
+
+class _Conv3x3Train(torch.autograd.Function):
+    """``conv3x3_train``: the forward kernel of ``conv3x3``, the input gradient on the same kernel and the weight / bias gradients of
+    ``csrc/vfa_conv_grad.hip``.  The packed planes are made per call and kept nowhere: a weight under training changes every step."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, dilation, stride, sizes):
+        packed, nbytes = _conv3x3_pack(weight)
+        ctx.save_for_backward(x, weight)
+        ctx.dilation, ctx.has_bias = dilation, bias is not None
+        return _conv3x3_launch(x, stride, packed, nbytes, None, bias, False, sizes, dilation)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        x, weight = ctx.saved_tensors
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = conv3x3_input_grad(grad, weight, ctx.dilation)
+        want_bias = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_bias:
+            dw, db = conv3x3_weight_grad(grad, x, ctx.dilation, want_bias=want_bias)
+            dw = dw if ctx.needs_input_grad[1] else None
+        return dx, dw, db, None, None, None
+
+
+def conv3x3_train(x, weight, bias=None, dilation=1):
+    """``F.conv2d(x, weight, bias, padding=dilation, dilation=dilation)`` with gradients, on the HIP kernels: x (B, C, L, W) float32
+    read through its strides, weight (O, C, 3, 3), C and O multiples of 32, bias (O) or None, dilation 1..4 -> (B, O, L, W)
+    contiguous, the same bits as ``conv3x3(x.detach(), weight.detach(), dilation, shift=bias)``.  Backward (once differentiable):
+    ``conv3x3_input_grad`` and ``conv3x3_weight_grad`` for the operands that require a gradient -- fixed summation order, no float
+    atomics, the same bits on every run without ``torch.use_deterministic_algorithms``; no host wait, capturable."""
+    stride, sizes = _conv_operands("conv3x3_train", x, weight, bias, inference=False)
+    B, C, L, W, O = sizes
+    if C % 32 or O % 32:
+        raise ValueError(f"conv3x3_train: C and O must be multiples of 32, got weight {tuple(weight.shape)}")
+    if not 1 <= int(dilation) <= 4:
+        raise ValueError(f"conv3x3_train: dilation must be 1..4, got {dilation}")
+    if bias is not None and bias.numel() != O:
+        raise ValueError(f"conv3x3_train: bias must have {O} values, got {tuple(bias.shape)}")
+    return _Conv3x3Train.apply(x, weight, bias, int(dilation), stride, sizes)
 
 
 def conv3x3_few(x, weight, dilation=1, affine=None):

@@ -15,6 +15,10 @@ Multi-GPU (``distributed=True``): each rank runs backbone + laterals + projectio
 ``head_convs="hip"`` (a plain attribute too; default ``"library"``) runs the dense 3x3 convolutions of the BEV heads at inference on
 the HIP kernels of ``csrc/vfa_conv.hip`` from the same parameters (``heads``).
 
+``head_convs_train="hip"`` (the same kind of attribute; default ``"library"``) runs the four 256 -> 256 convolutions of the heads
+WITH gradients on ``ops.conv3x3_train`` -- HIP forward, input-gradient and weight-gradient kernels (``csrc/vfa_conv_grad.hip``), the
+same bits on every run -- while the norms, the ReLUs and the few-output layers stay the modules they are (``heads``).
+
 ``trunk_convs="hip"`` (the same kind of attribute; default ``"library"``) runs the residual stages ``layer1`` .. ``layer4`` of the
 ResNet trunk at inference on the HIP kernels of ``csrc/vfa_trunk.hip`` from the same parameters (``trunk``).
 
@@ -47,6 +51,8 @@ FUSE_PRODUCER_TRAIN = os.environ.get("VFA_AMD_FUSE_PRODUCER_TRAIN", "0") == "1"
 PRETRAINED_ENV = "VFA_AMD_PRETRAINED"
 # Who runs the dense 3x3 convolutions of the BEV heads (``VFANet.head_convs``, ``VFANet.heads(convs=...)``)
 HEAD_CONVS = ("library", "hip")
+# Who runs the four 256 -> 256 convolutions of the BEV heads where gradients are enabled (``VFANet.head_convs_train``)
+HEAD_CONVS_TRAIN = ("library", "hip")
 # Who runs the residual stages of the trunk (``VFANet.trunk_convs``, ``VFANet.trunk``)
 TRUNK_CONVS = ("library", "hip")
 # Who runs the trunk's stem (``VFANet.trunk_stem``, ``VFANet.trunk``)
@@ -198,6 +204,7 @@ class VFANet(nn.Module):
         self.mode = mode
         self.view_reduce = check_view_reduce(view_reduce)
         self.head_convs = "library"  # or "hip" (``heads``); a plain attribute like ``view_reduce``: no ``state_dict`` key
+        self.head_convs_train = "library"  # or "hip" (``heads``, with gradients); the same kind of attribute
         self.trunk_convs = "library"  # or "hip" (``trunk``); the same kind of attribute
         self.trunk_stem = "library"  # or "hip" (``trunk``); the same kind of attribute, independent of ``trunk_convs``
         self.input_size = getattr(args, "resize_size", None)  # (H, W) uint8 frames are resized to (train.py:209-214); None: as they are
@@ -378,6 +385,24 @@ class VFANet(nn.Module):
             x = ops.conv3x3(x, conv.weight, conv.dilation[0], scale=scale, shift=shift, relu=True)
         return x
 
+    def _hip_train_ok(self, topdown):
+        """``head_convs_train = "hip"`` covers what ``ops.conv3x3_train`` does: gradients enabled, a float32 CUDA map of 256
+        channels.  Anything else runs the library path."""
+        return (torch.is_grad_enabled() and topdown.is_cuda and topdown.dtype == torch.float32 and topdown.dim() == 4
+                and topdown.shape[1] == 256 and topdown.numel() > 0)
+
+    @staticmethod
+    def _train_conv(conv, x):
+        return ops.conv3x3_train(x, conv.weight, conv.bias, conv.dilation[0])
+
+    def _train_fuse(self, topdown):
+        """``fuse`` with its two convolutions on ``ops.conv3x3_train``; BatchNorm (training or eval mode) and ReLU as they are."""
+        return self.fuse[4:](self._train_conv(self.fuse[3], self.fuse[1:3](self._train_conv(self.fuse[0], topdown))))
+
+    def _train_head(self, topdown, head):
+        """``_head`` with its 256 -> 256 convolution on ``ops.conv3x3_train``; GroupNorm, ReLU and the few-output layer as they are."""
+        return head[1:](self._train_conv(head[0], topdown))
+
     def heads(self, topdown, rotation_at=None, convs=None):
         """The BEV heads on the fused map (reference vfanet.py:131-149).
 
@@ -385,6 +410,10 @@ class VFANet(nn.Module):
         ``tytx_pred`` and ``thtwtl_pred`` as the modules they are; ``"hip"`` runs them at inference on ``ops.conv3x3`` /
         ``ops.conv3x3_few`` / ``ops.group_norm_affine`` -- the same function of the same parameters up to the summation order
          -- where ``_hip_convs_ok`` holds, and the library path otherwise.
+
+        The attribute ``head_convs_train`` (``"library"`` or ``"hip"``) is the same choice where gradients are enabled: ``"hip"``
+        runs ``fuse[0]``, ``fuse[3]``, ``tytx_pred[0]`` and ``thtwtl_pred[0]`` on ``ops.conv3x3_train`` where ``_hip_train_ok``
+        holds -- differentiable, the same bits on every run -- and every other layer as the module it is.
 
         ``rotation_at`` (3D only, ``ValueError`` in 2D) evaluates ``orient_pred`` -- the largest layer of the heads, read at a few
         dozen cells -- only where it is read, on ``ops.conv3x3_at_cells`` instead of a dense convolution; the other heads are the
@@ -398,17 +427,25 @@ class VFANet(nn.Module):
         convs = self.head_convs if convs is None else convs
         if convs not in HEAD_CONVS:
             raise ValueError(f"VFANet.heads: convs is one of {HEAD_CONVS}, got {convs!r}")
+        if self.head_convs_train not in HEAD_CONVS_TRAIN:
+            raise ValueError(f"VFANet.heads: head_convs_train is one of {HEAD_CONVS_TRAIN}, got {self.head_convs_train!r}")
         hip = convs == "hip" and self._hip_convs_ok(topdown)
+        train = self.head_convs_train == "hip" and self._hip_train_ok(topdown)  # (never both: ``hip`` needs gradients off)
         if hip:
             fused = self._hip_fuse(topdown)
             conv = self.map_classifier[0]
             out = {"heatmap": ops.conv3x3_few(fused, conv.weight, conv.dilation[0]),
                    "loc_offset": self._hip_head(topdown, self.tytx_pred).permute(0, 2, 3, 1)}
+        elif train:
+            fused = self._train_fuse(topdown)
+            out = {"heatmap": self.map_classifier(fused), "loc_offset": self._train_head(topdown, self.tytx_pred).permute(0, 2, 3, 1)}
         else:
             fused = self.fuse(topdown)
             out = {"heatmap": self.map_classifier(fused), "loc_offset": self.tytx_pred(topdown).permute(0, 2, 3, 1)}
         if self.mode == "3D":
-            out["dim_offset"] = (self._hip_head(topdown, self.thtwtl_pred) if hip else self.thtwtl_pred(topdown)).permute(0, 2, 3, 1)
+            dim = (self._hip_head(topdown, self.thtwtl_pred) if hip else self._train_head(topdown, self.thtwtl_pred) if train
+                   else self.thtwtl_pred(topdown))
+            out["dim_offset"] = dim.permute(0, 2, 3, 1)
             conv = self.orient_pred[0]
             if rotation_at is None:
                 out["rotation"] = self.orient_pred(fused).permute(0, 2, 3, 1)
