@@ -885,7 +885,7 @@ int vfa_image_plan(int Hin, int Win, int Hout, int Wout, const float *mean, cons
 int vfa_image_frames_u8_f32(const unsigned char *src, long long image_stride_bytes, long long row_stride_bytes, int N, int Hin, int Win,
                             const void *workspace, size_t workspace_bytes, float *dst, int Hout, int Wout, void *stream);
 
-/* ---- the dense 3x3 convolutions of the BEV heads at inference (csrc/vfa_conv.hip; the integer rules: csrc/vfa_conv.h) -------------
+/* ---- the dense 3x3 convolutions of the BEV heads at inference (csrc/vfa_conv.hip, vfa_dense.h; the rules: csrc/vfa_conv.h) -------------
  *                         replaces the nn.Conv2d / BatchNorm2d / GroupNorm calls of vfanet.py:131-149 in eval mode
  * All of them: stride 1, zero padding = dilation, 1 <= dilation <= 4, float32; x (B, C, L, W) is read through its four ELEMENT
  * strides x_stride[4] (>= 0: NCHW, channels-last or a slice; never copied), out is contiguous (B, O, L, W) and every element is
@@ -954,7 +954,7 @@ size_t vfa_conv3x3_wgrad_workspace_bytes(int B, int O, int C, int L, int W);
 int vfa_conv3x3_wgrad_f32(const float *g, const long long *g_stride, const float *x, const long long *x_stride, int B, int C, int L, int W,
                           int O, int dilation, float *dw, float *db, void *workspace, size_t workspace_bytes, void *stream);
 
-/* ---- the residual stages of the ResNet trunk at inference (csrc/vfa_trunk.hip; the integer rules: csrc/vfa_trunk.h) ----------------
+/* ---- the residual stages of the ResNet trunk at inference (csrc/vfa_trunk.hip, vfa_dense.h; the rules: csrc/vfa_conv.h) ----------------
  *                         replaces the nn.Conv2d / GroupNorm / ReLU calls of a block, resnet.py:26-57, in eval mode
  * The dense kernel above with a stride, one or nine taps and a prologue; float32; x (B, C, L, W) is read through its four ELEMENT
  * strides x_stride[4] (>= 0, never copied).  Fixed summation order and no float atomics: the same bits on every run, and an image

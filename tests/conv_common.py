@@ -1,6 +1,6 @@
 """What the tests of the heads' dense 3x3 convolutions share (tests/test_head_convs_cpu.py, tests/test_head_convs.py): the two
 yardsticks against the float64 ``F.conv2d`` of the same float32 inputs on the CPU, and a numpy restatement of the kernels'
-arithmetic (vfa_amd/csrc/vfa_conv.hip) on which the yardsticks are shown to discriminate before a GPU sees them.
+arithmetic (vfa_amd/csrc/vfa_conv.hip, vfa_dense.h) on which the yardsticks are shown to discriminate before a GPU sees them.
 
 (E) elementwise, the raw convolution:  |y - y64| <= gamma_n (|x| conv |w|),  gamma_n = n u / (1 - n u),  u = 2^-24.
     Dense kernel: n = 27 C + 12 -- three products of 9 C terms in any order, 8 u for the two split residuals (2^-23 of each operand,
@@ -13,7 +13,7 @@ import torch
 import torch.nn.functional as F
 
 U = 2.0 ** -24
-EXP = 14            # kExp of vfa_conv.hip
+EXP = 14            # kExp of vfa_dense.h
 EXP_LIMIT = 40      # kExpLim of vfa_split.h
 CHUNK, STEP = 32, 16
 N_MARGIN = 4.0

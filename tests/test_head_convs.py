@@ -459,3 +459,27 @@ def test_detect_runs_with_hip_head_convs():
     if stable:
         for k in found:                                       # (the fused map in front of the heads is the same: so is everything behind it)
             assert torch.equal(found[k], again[k]), k
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs (the dynamic-LDS attribute is per device)")
+def test_a_second_device_runs_the_dense_kernels_after_the_first():
+    """The kernels need 65-108 KB of dynamic LDS, which is allowed per kernel AND per device: a process that has run them on device 0
+    runs them on device 1 -- the forward (d = 4, the largest window) and ``conv3x3_train`` forward and backward (the weight
+    gradient's kernel has its own allowance) -- with the bits of device 0."""
+    from vfa_amd import ops
+    x, w = cc.inputs(2, 32, 40, 9, 11, seed=31)
+    xt, wt = cc.inputs(2, 32, 32, 9, 11, seed=32)
+
+    def run(dev):
+        with torch.cuda.device(dev):
+            with torch.no_grad():
+                y = ops.conv3x3(x.to(dev), w.to(dev), dilation=4)
+            xd, wd = xt.to(dev).requires_grad_(), wt.to(dev).requires_grad_()
+            yt = ops.conv3x3_train(xd, wd, dilation=2)
+            yt.backward(torch.ones_like(yt))
+            torch.cuda.synchronize(dev)
+            return [t.detach().cpu() for t in (y, yt, xd.grad, wd.grad)]
+    first, second = run(torch.device("cuda:0")), run(torch.device("cuda:1"))
+    assert float(first[0].abs().max()) > 0 and float(first[3].abs().max()) > 0
+    for name, a, b in zip(("conv3x3", "conv3x3_train", "input gradient", "weight gradient"), first, second):
+        assert torch.equal(_bits(a), _bits(b)), name

@@ -166,6 +166,18 @@ def test_same_bits_on_every_run_alone_and_in_a_batch_and_in_every_layout(k, stri
         assert torch.equal(_bits(first[b:b + 1]), _bits(alone[b])), f"image {b} alone"
 
 
+@pytest.mark.parametrize("layout", ["nchw", "nhwc"])
+def test_the_trunk_and_the_heads_give_the_same_bits_where_they_are_the_same_convolution(layout):
+    """Three by three, stride 1, dilation 1, no prologue and no epilogue operands: one kernel with two epilogues."""
+    from vfa_amd import ops
+    x, w = cc.inputs(2, 64, 130, 9, 37, seed=93)
+    with torch.no_grad():
+        trunk = ops.trunk_conv(_layout(x, layout), w.to(DEV), 1)
+        heads = ops.conv3x3(_layout(x, layout), w.to(DEV), 1)
+    assert float(trunk.abs().max()) > 0 and trunk.shape == heads.shape
+    assert torch.equal(_bits(trunk), _bits(heads))
+
+
 def test_all_zero_input_gives_zeros():
     from vfa_amd import ops
     x, w = tc.inputs(2, 64, 130, 9, 37, seed=95)

@@ -1,4 +1,4 @@
-"""The trunk's convolutions without a GPU: the integer rules of vfa_amd/csrc/vfa_trunk.h (shared host / device code) compiled with g++
+"""The trunk's convolutions without a GPU: the integer rules of vfa_amd/csrc/vfa_conv.h (shared host / device code) compiled with g++
 into tests/native/trunk_harness.cpp and checked against brute force, once more as a stand-alone program under the host sanitizers;
 the numpy restatement of the kernels' arithmetic (tests/trunk_common.py) against the two yardsticks, with the restatement that drops
 the lo pieces failing (N); a restated ResNet-18 trunk against the float64 trunk; what the entry points refuse before they launch; the

@@ -1,6 +1,6 @@
 """What the tests of the trunk's convolutions share (tests/test_trunk_convs_cpu.py, tests/test_trunk_convs.py): the yardsticks of
 tests/conv_common.py with a stride, a 1 x 1 weight and the prologue, and a numpy restatement of the arithmetic of
-vfa_amd/csrc/vfa_trunk.hip -- the convolution, the GroupNorm affine, the join, a block and the whole trunk.
+vfa_amd/csrc/vfa_trunk.hip (the dense kernel of vfa_dense.h) -- the convolution, the GroupNorm affine, the join, a block and the whole trunk.
 
 (E) elementwise:  |y - y64| <= gamma_n (|x'| conv |w|),  n = 27 C + 12 with nine taps and 3 C + 12 with one: three products of
     taps x C terms in any order, the split residuals, the dropped lo.lo, the scaling.  x' is the FLOAT32 result of the prologue
@@ -15,7 +15,7 @@ import torch.nn.functional as F
 
 import conv_common as cc
 
-SPLIT_C = 256       # kSplitC of vfa_trunk.h
+SPLIT_C = 256       # kSplitC of vfa_conv.h
 
 
 def n_trunk(C, taps):

@@ -7,7 +7,7 @@
 // order, no float atomics: the same bits on every run.  (The input gradient is the forward kernel on g with the transposed,
 // tap-mirrored weight: vfa_conv3x3_pack_weights_transposed_f32.)  The integer rules: vfa_conv_grad.h.
 //
-//   1. conv_absmax_kernel of vfa_conv.hip on g and on x: per frame the power-of-two scale of the fp16 split (vfa_split.h).
+//   1. absmax_kernel of vfa_dense.h (vfa_conv::frame_absmax) on g and on x: per frame the power-of-two scale of the fp16 split (vfa_split.h).
 //   2. wgrad_kernel<D>: an implicit GEMM with M = outputs, N = inputs, K = cells, once per tap.  A workgroup of 4 waves owns one
 //      (frame, slab of cells) and a tile of 128 outputs x 32 inputs x 9 taps; wave w takes the outputs 32 w .. 32 w + 31: nine 32 x 32
 //      accumulators.  K runs in the forward kernel's tiles of 4 map rows x 32 columns: the tile's cells of g (128 outputs) and the
@@ -262,12 +262,9 @@ size_t scales_bytes(int B) { return ((size_t)2 * B * sizeof(unsigned) + 255) / 2
 template <int D>
 int launch_wgrad(const Map &mg, const Map &mx, const unsigned *absmax, int B, int C, int L, int W, int O, float *partial, hipStream_t s)
 {
-    static bool attr_set = false; // idempotent: a race only repeats the call
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute((const void *)wgrad_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, Grad<D>::kLdsBytes);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    static DynamicLds lds; // (vfa_conv.h: once per device)
+    const int status = lds.allow((const void *)wgrad_kernel<D>, Grad<D>::kLdsBytes);
+    if (status != 0) return status;
     const dim3 grid((unsigned)slabs(L, W), (unsigned)(((O + kTileO - 1) / kTileO) * (C / kTileC)), (unsigned)B);
     hipLaunchKernelGGL(wgrad_kernel<D>, grid, dim3(kThreads), Grad<D>::kLdsBytes, s, mg, mx, absmax, B, C, L, W, O, partial);
     return (int)hipGetLastError();

@@ -10,7 +10,7 @@
 // position (2 ry + ky, 2 rx + kx) of channel c.
 // Where a window position lies in LDS is its LOCATION: rows of kWinPitch floats, the even window columns of a row first and the odd
 // ones behind them, so that the 32 cells of an MFMA operand -- window columns 2 rx + kx -- read 32 CONSECUTIVE locations (the rule of
-// vfa_trunk.h at stride 2).  location = cell_base(ry, rx) + tap_offset(k): the second term is the same for every lane of an operand.
+// vfa_conv.h at stride 2).  location = cell_base(ry, rx) + tap_offset(k): the second term is the same for every lane of an operand.
 //
 // Packed weight: kKPad rows of 64 floats, row k holding (output r, output 32 + r) pairs for r = 0 .. 31 -- the two A operands of a
 // lane as one 8-byte read; outputs past O and the row k = 147 are zeros.
