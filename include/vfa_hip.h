@@ -987,6 +987,49 @@ int vfa_trunk_conv_f32(const float *x, const long long *x_stride, const void *pa
 int vfa_residual_join_f32(const float *y, const float *a, const float *b, const float *r, const float *ra, const float *rb, int B, int C, int L,
                           int W, float *out, void *stream);
 
+/* ---- training the identity residual blocks of the trunk (csrc/vfa_trunk_grad.hip, vfa_conv_grad.hip, vfa_conv.hip) ---------------------
+ *                         replaces the backward of a BasicBlock of resnet.py:26-57 with stride 1 and no projection
+ * A block keeps three maps (the two raw convolutions y1, y2 and the join) besides its input; the normalised maps are recomputed in
+ * prologues.  float32, fixed summation order, no float atomics: the same bits on every run, and an image gives the same dx bits
+ * alone and in a batch.  Stream-ordered, no host wait, capturable; workspaces are the caller's, the library keeps no state.
+ * The input gradient of a stride-1 layer needs no entry point of its own: vfa_conv3x3_pack_weights_transposed_f32 writes the planes
+ * vfa_trunk_conv_f32 reads (taps 9, stride 1, no prologue, C' = O, O' = C), two accumulator chains past 256 channels included.
+ *
+ * vfa_group_norm_stats_f32: vfa_group_norm_affine_f32 -- the same kernels, a and b bit for bit -- that also writes stats
+ *   (B, groups, 2) doubles (8-byte aligned): the mean and rstd = 1 / sqrt(var + eps) of each (image, group), the float64 values a and
+ *   b were made from.
+ * vfa_group_norm_backward_f32: the backward of z = GroupNorm(y) behind a ReLU with mask m, u being the gradient behind that ReLU;
+ *   y, u, out, dy, dz contiguous (B, C, L, W), no two of them the same memory.  mask VFA_GN_MASK_PROLOGUE: m = fmaf(a[b, c], y,
+ *   b[b, c]) > 0 with the forward's (B, C) affine -- the ReLU the next convolution applied as it read y; out, dz unused.
+ *   VFA_GN_MASK_OUT: m = out > 0 for the given map -- the ReLU of the join -- and dz = m ? u : 0, the gradient of the shortcut, is
+ *   written too; a, b unused.  Three launches: per (image, channel) S1 = sum m u and S2 = sum m u y in float64 (32 parts of the
+ *   plane, a fixed tree in each, the parts in ascending order); per (image, channel) the float64 coefficients p = gamma rstd, q, r of
+ *   dy = p (m u) + q y + r, each rounded to float32 once, and dgamma[c], dbeta[c] (C floats, either may be NULL) as float64 sums over
+ *   the images in ascending order, rounded once; elementwise dy = fmaf(p, m ? u : 0, fmaf(q, y, r)) (a NaN stays a NaN).  gamma:
+ *   C floats or NULL (1); stats: those of vfa_group_norm_stats_f32.  workspace: vfa_group_norm_backward_workspace_bytes(B, C) bytes,
+ *   8-byte aligned.
+ * vfa_trunk_conv_wgrad_f32: vfa_conv3x3_wgrad_f32 at dilation 1 without db, whose x operand is max(fmaf(a[b, c], x, b[b, c]), 0)
+ *   where a, b ((B, C) floats, both or neither) are given -- applied as a value of the window arrives, a position outside the map
+ *   being a zero AFTER that, and seen by the absmax pre-pass -- and x itself where they are NULL.  The cells are cut into
+ *   slabs_for(L, W, O, C) slabs (csrc/vfa_conv_grad.h): the slabs of vfa_conv3x3_wgrad_f32 up to O * C = 256^2 (there, without a and
+ *   b, its bits), fewer in proportion past it, so that a frame's partials never exceed those of a 256 x 256 layer on the same map;
+ *   partial layout and merge are unchanged.  workspace: vfa_trunk_conv_wgrad_workspace_bytes(B, O, C, L, W) bytes, 16-byte aligned.
+ *
+ * Errors, decided before anything is launched: as for the entry points above; a mask other than the two, one of a / b without the
+ * other, groups that do not divide C: VFA_ERR_BAD_ARGUMENT; the backward with B, C or L > 65535, L * W >= 2^30 or B * C >= 2^29:
+ * VFA_ERR_UNSUPPORTED.  B == 0 or L * W == 0: dgamma, dbeta (and dw) are zeros, nothing else is written. */
+#define VFA_GN_MASK_PROLOGUE 0
+#define VFA_GN_MASK_OUT 1
+int vfa_group_norm_stats_f32(const float *x, const long long *x_stride, const float *gamma, const float *beta, float eps, int B, int C,
+                             int L, int W, int groups, float *a, float *b, double *stats, void *workspace, size_t workspace_bytes, void *stream);
+size_t vfa_group_norm_backward_workspace_bytes(int B, int C);
+int vfa_group_norm_backward_f32(const float *y, const float *u, const float *a, const float *b, const float *out, const float *gamma,
+                                const double *stats, int mask, int B, int C, int L, int W, int groups, float *dy, float *dz, float *dgamma,
+                                float *dbeta, void *workspace, size_t workspace_bytes, void *stream);
+size_t vfa_trunk_conv_wgrad_workspace_bytes(int B, int O, int C, int L, int W);
+int vfa_trunk_conv_wgrad_f32(const float *g, const long long *g_stride, const float *x, const long long *x_stride, const float *a, const float *b,
+                             int B, int C, int L, int W, int O, float *dw, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- the stem of the ResNet trunk at inference (csrc/vfa_stem.hip; the integer rules: csrc/vfa_stem.h) ------------------------------
  *                         replaces conv1 and the max pooling of resnet.py:100-102, 139-140 in eval mode
  * float32; fixed summation order and no atomics: the same bits on every run, and an image gives the same bits alone and in a

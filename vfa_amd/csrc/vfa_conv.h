@@ -123,6 +123,8 @@ VFA_CONV_HD size_t packed_index(int o, int c, int t, int piece, int C) { return 
 // integer atomicMax: the caller zeroes absmax[0 .. B - 1] on the stream first) -- the operand's power-of-two scale of vfa_split.h.
 // x (B, C, L, W) is read through its four element strides.  0, or the error of the entry points (an empty map launches nothing).
 int frame_absmax(const float *x, const long long *stride, int B, int C, int L, int W, unsigned *absmax, void *stream);
+// ... of the values max(fmaf(a[b, c], x, b[b, c]), 0) behind the prologue of vfa_dense.h (a, b: (B, C) floats, or both nullptr: x itself)
+int frame_absmax(const float *x, const long long *stride, const float *a, const float *b, int B, int C, int L, int W, unsigned *absmax, void *stream);
 
 #if defined(__HIPCC__)
 // host side: hipFuncAttributeMaxDynamicSharedMemorySize belongs to a kernel ON A DEVICE, so a launcher keeps one of these per kernel

@@ -12,7 +12,8 @@
 //      quarter of the channels each (channel-ascending, tap-ascending chains), merged as (p0 + p1) + (p2 + p3).  Optional
 //      prologue relu(a[b, c] x + b[b, c]) applied as a tap is read; a tap outside the map is a zero AFTER the prologue.
 //   3. gn_partial_kernel / gn_affine_kernel: per (frame, group) sum and sum of squares in float64 (32 parts in a fixed tree, merged
-//      in ascending order), then a = gamma rstd, b = beta - mean a per (frame, channel).
+//      in ascending order), then a = gamma rstd, b = beta - mean a per (frame, channel); where the caller keeps them for a backward
+//      (vfa_group_norm_stats_f32), the mean and rstd of each (frame, group) as the float64 values a and b were made from.
 //   4. bn_fold_kernel: scale = gamma / sqrt(var + eps), shift = beta + (bias - mean) scale from the running statistics on the device.
 #include "vfa_dense.h"
 
@@ -100,10 +101,10 @@ __global__ __launch_bounds__(kThreads) void gn_partial_kernel(const Map m, int g
     }
 }
 
-// one thread per (frame, channel)
+// one thread per (frame, channel); stats (nullptr: not wanted): (B, groups, 2) mean | rstd, written by the group's first channel
 __global__ __launch_bounds__(kThreads) void gn_affine_kernel(const double *__restrict__ partial, const float *__restrict__ gamma,
                                                              const float *__restrict__ beta, double eps, int B, int C, int groups, double count,
-                                                             float *__restrict__ a, float *__restrict__ bb)
+                                                             float *__restrict__ a, float *__restrict__ bb, double *__restrict__ stats)
 {
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= B * C) return;
@@ -121,6 +122,10 @@ __global__ __launch_bounds__(kThreads) void gn_affine_kernel(const double *__res
     const double ga = gamma ? (double)gamma[c] : 1.0, be = beta ? (double)beta[c] : 0.0;
     a[i] = (float)(ga * rstd);
     bb[i] = (float)(be - mean * ga * rstd);
+    if (stats && c == g * (C / groups)) {
+        stats[((size_t)b * groups + g) * 2] = mean;
+        stats[((size_t)b * groups + g) * 2 + 1] = rstd;
+    }
 }
 
 __global__ __launch_bounds__(kThreads) void bn_fold_kernel(const float *__restrict__ gamma, const float *__restrict__ beta, const float *__restrict__ mean,
@@ -140,14 +145,38 @@ int launch_heads(const Map &m, const unsigned *absmax, const unsigned char *pack
     return launch_dense<kTaps, 1, D, false, false>(m, nullptr, nullptr, absmax, packed, epi, O, out, s);
 }
 
+// the two launches of the GroupNorm affine; stats: nullptr, or where the (frame, group) mean | rstd go
+int group_norm(const float *x, const long long *x_stride, const float *gamma, const float *beta, float eps, int B, int C, int L, int W, int groups,
+               float *a, float *b, double *stats, void *workspace, size_t workspace_bytes, void *stream)
+{
+    Map m = {};
+    if (groups < 1 || C < 1 || C % groups != 0) return VFA_ERR_BAD_ARGUMENT;
+    const int status = check_map(x, x_stride, B, C, L, W, m);
+    if (status != 0) return status == 1 ? 0 : status;
+    if (!a || !b || !workspace || ((uintptr_t)workspace & 7) != 0 || workspace_bytes < vfa_group_norm_workspace_bytes(B, groups))
+        return VFA_ERR_BAD_ARGUMENT;
+    if (groups > 65535 || (long long)B * C > INT32_MAX) return VFA_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(gn_partial_kernel, dim3(kGnParts, (unsigned)groups, (unsigned)B), dim3(kThreads), 0, s, m, groups, (double *)workspace);
+    hipLaunchKernelGGL(gn_affine_kernel, dim3((unsigned)((B * C + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (const double *)workspace,
+                       gamma, beta, (double)eps, B, C, groups, (double)(C / groups) * (double)L * (double)W, a, b, stats);
+    return (int)hipGetLastError();
+}
+
 } // namespace
 
 int vfa_conv::frame_absmax(const float *x, const long long *stride, int B, int C, int L, int W, unsigned *absmax, void *stream)
 {
+    return frame_absmax(x, stride, nullptr, nullptr, B, C, L, W, absmax, stream);
+}
+
+int vfa_conv::frame_absmax(const float *x, const long long *stride, const float *a, const float *b, int B, int C, int L, int W, unsigned *absmax,
+                           void *stream)
+{
     Map m = {};
     const int status = check_map(x, stride, B, C, L, W, m);
     if (status != 0) return status == 1 ? 0 : status;
-    launch_absmax(m, nullptr, nullptr, L, W, 1, absmax, (hipStream_t)stream);
+    launch_absmax(m, a, b, L, W, 1, absmax, (hipStream_t)stream);
     return (int)hipGetLastError();
 }
 
@@ -233,18 +262,14 @@ size_t vfa_group_norm_workspace_bytes(int B, int groups)
 int vfa_group_norm_affine_f32(const float *x, const long long *x_stride, const float *gamma, const float *beta, float eps, int B, int C,
                               int L, int W, int groups, float *a, float *b, void *workspace, size_t workspace_bytes, void *stream)
 {
-    Map m = {};
-    if (groups < 1 || C < 1 || C % groups != 0) return VFA_ERR_BAD_ARGUMENT;
-    const int status = check_map(x, x_stride, B, C, L, W, m);
-    if (status != 0) return status == 1 ? 0 : status;
-    if (!a || !b || !workspace || ((uintptr_t)workspace & 7) != 0 || workspace_bytes < vfa_group_norm_workspace_bytes(B, groups))
-        return VFA_ERR_BAD_ARGUMENT;
-    if (groups > 65535 || (long long)B * C > INT32_MAX) return VFA_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(gn_partial_kernel, dim3(kGnParts, (unsigned)groups, (unsigned)B), dim3(kThreads), 0, s, m, groups, (double *)workspace);
-    hipLaunchKernelGGL(gn_affine_kernel, dim3((unsigned)((B * C + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (const double *)workspace,
-                       gamma, beta, (double)eps, B, C, groups, (double)(C / groups) * (double)L * (double)W, a, b);
-    return (int)hipGetLastError();
+    return group_norm(x, x_stride, gamma, beta, eps, B, C, L, W, groups, a, b, nullptr, workspace, workspace_bytes, stream);
+}
+
+int vfa_group_norm_stats_f32(const float *x, const long long *x_stride, const float *gamma, const float *beta, float eps, int B, int C,
+                             int L, int W, int groups, float *a, float *b, double *stats, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!stats || ((uintptr_t)stats & 7) != 0) return VFA_ERR_BAD_ARGUMENT;
+    return group_norm(x, x_stride, gamma, beta, eps, B, C, L, W, groups, a, b, stats, workspace, workspace_bytes, stream);
 }
 
 } // extern "C"

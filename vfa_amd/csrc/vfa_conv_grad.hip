@@ -17,6 +17,10 @@
 //      transposed LDS read, delivers it.  A tap moves the window location of a cell, never the alignment of a read, so the nine
 //      taps read the one window at nine offsets.  A product is the three v_mfma_f32_32x32x16_f16 of vfa_split.h (g_lo x_hi, g_hi x_hi,
 //      g_hi x_lo).  Epilogue: the partial acc 2^-(eg + ex) of the frame's two scales to the workspace, [frame][slab][tap][o][c].
+//      PRO (the trunk's layers, vfa_trunk_conv_wgrad_f32, wgrad_kernel<1, true>): the x operand is max(fmaf(a[b, c], x, b[b, c]), 0), the
+//      GroupNorm affine and the ReLU in front of the convolution, applied in x_load as a value arrives; a window position outside the
+//      map is a zero AFTER that.  a | b of the workgroup's 32 inputs lie behind the planes in LDS, read from memory once; the absmax
+//      pre-pass sees the same values.  Without PRO that region does not exist and pa, pb are not read.
 //   3. wgrad_merge_kernel: per element of dW the partials in ascending (frame, slab) order, summed in float64, rounded once.
 //   4. bias_grad_kernel: per output a workgroup; thread i sums the cells i, i + 256, .. of frame 0, then of frame 1, .. in float64,
 //      the 256 sums are merged in a fixed tree and rounded once.
@@ -54,7 +58,9 @@ template <int D> struct Grad {
     static constexpr int kQuads = kLoc * (kTileC / 4);
     static constexpr int kLoads = (kQuads + kThreads - 1) / kThreads;
     static constexpr int kPlaneHalves = kLoc * kLocHalves;
-    static constexpr int kLdsBytes = (2 * kPlaneHalves + 2 * kGPlaneHalves) * 2;
+    static constexpr int kPlaneBytes = (2 * kPlaneHalves + 2 * kGPlaneHalves) * 2;
+    static constexpr int kLdsBytes = kPlaneBytes;                                      // without the prologue
+    static constexpr int kLdsBytesPro = kPlaneBytes + 2 * kTileC * (int)sizeof(float); // a | b of the tile's inputs behind the planes
 };
 
 // quad e of the window of x: (location, four inputs 4 c4 .. 4 c4 + 3), consecutive threads on consecutive addresses of the map
@@ -70,8 +76,17 @@ __device__ __forceinline__ void g_quad_of(int e, bool chan_fast, int &cell, int 
     else { c4 = e / kTileCells; cell = e & (kTileCells - 1); }
 }
 
-template <int D>
-__device__ __forceinline__ void x_load(const Map m, int L, int W, int b, int y0, int x0, int c0, bool chan_fast, int tid, float (&v)[Grad<D>::kLoads][4])
+__device__ __forceinline__ float prologue(float a, float x, float b)
+{
+    const float t = fmaf(a, x, b);
+    return t < 0.0f ? 0.0f : t; // (a NaN stays a NaN)
+}
+
+// PRO: a value inside the map becomes max(fmaf(a, x, b), 0) with a | b of the tile's inputs in `ab`; a position outside the map is a
+// zero, after that
+template <int D, bool PRO>
+__device__ __forceinline__ void x_load(const Map m, const float *ab, int L, int W, int b, int y0, int x0, int c0, bool chan_fast, int tid,
+                                       float (&v)[Grad<D>::kLoads][4])
 {
 #pragma unroll
     for (int j = 0; j < Grad<D>::kLoads; ++j) {
@@ -80,8 +95,12 @@ __device__ __forceinline__ void x_load(const Map m, int L, int W, int b, int y0,
         x_quad_of<D>(e, chan_fast, loc, c4);
         const bool ok = e < Grad<D>::kQuads && window_position(loc, y0, x0, D, L, W, y, x);
         const float *p = m.x + (ok ? b * m.s_frame + (long long)(c0 + 4 * c4) * m.s_chan + y * m.s_row + x * m.s_col : 0);
+        const int cq = ok ? 4 * c4 : 0; // (PRO)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[j][k] = ok ? p[k * m.s_chan] : 0.0f;
+        for (int k = 0; k < 4; ++k) {
+            if constexpr (PRO) v[j][k] = ok ? prologue(ab[cq + k], p[k * m.s_chan], ab[kTileC + cq + k]) : 0.0f;
+            else v[j][k] = ok ? p[k * m.s_chan] : 0.0f;
+        }
     }
 }
 
@@ -145,12 +164,14 @@ __device__ __forceinline__ f16x8 operand(const _Float16 *p, int step)
     return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-template <int D>
-__global__ __launch_bounds__(kThreads) void wgrad_kernel(const Map mg, const Map mx, const unsigned *__restrict__ absmax, int B, int C, int L, int W,
-                                                         int O, float *__restrict__ partial)
+template <int D, bool PRO = false>
+__global__ __launch_bounds__(kThreads) void wgrad_kernel(const Map mg, const Map mx, const float *__restrict__ pa, const float *__restrict__ pb,
+                                                         const unsigned *__restrict__ absmax, int B, int C, int L, int W, int O,
+                                                         float *__restrict__ partial)
 {
     extern __shared__ __align__(16) unsigned char lds[];
     _Float16 *x_hi = (_Float16 *)lds, *x_lo = x_hi + Grad<D>::kPlaneHalves, *g_hi = x_lo + Grad<D>::kPlaneHalves, *g_lo = g_hi + kGPlaneHalves;
+    const float *ab = (const float *)(lds + Grad<D>::kPlaneBytes); // (PRO)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int slab = blockIdx.x, b = blockIdx.z, n_c = C / kTileC;
@@ -158,7 +179,8 @@ __global__ __launch_bounds__(kThreads) void wgrad_kernel(const Map mg, const Map
     const bool g_fast = mg.s_chan == 1, x_fast = mx.s_chan == 1;
     const int eg = vfa_dev::split_exponent(absmax[b], kExp), ex = vfa_dev::split_exponent(absmax[B + b], kExp);
     const float sg = vfa_dev::pow2f(eg), sx = vfa_dev::pow2f(ex);
-    const int tile_begin = slab_begin(slab, L, W), tile_end = slab_begin(slab + 1, L, W);
+    const int n_slabs = (int)gridDim.x; // slabs(L, W), or the trunk's slabs_for(L, W, O, C)
+    const int tile_begin = slab_begin_of(slab, n_slabs, L, W), tile_end = slab_begin_of(slab + 1, n_slabs, L, W);
 
     // this lane's part of the transposed reads: row q of its group's block is cell 8 h + q of the step, columns 4 p .. of the
     // group's 16 channels
@@ -168,7 +190,11 @@ __global__ __launch_bounds__(kThreads) void wgrad_kernel(const Map mg, const Map
     float vx[Grad<D>::kLoads][4], vg[kGLoads][4];
     int y0, x0;
     tile_origin(tile_begin, W, y0, x0);
-    x_load<D>(mx, L, W, b, y0, x0, c0, x_fast, tid, vx);
+    if constexpr (PRO) { // a | b of this workgroup's inputs, once: threads 0 .. 63
+        if (tid < 2 * kTileC) ((float *)(lds + Grad<D>::kPlaneBytes))[tid] = (tid < kTileC ? pa : pb)[(size_t)b * C + c0 + (tid & (kTileC - 1))];
+        __syncthreads();
+    }
+    x_load<D, PRO>(mx, ab, L, W, b, y0, x0, c0, x_fast, tid, vx);
     g_load(mg, L, W, O, b, y0, x0, o0, g_fast, tid, vg);
     vfa_dev::fp16_saturate_mode(true);
     x_store<D>(x_hi, x_lo, sx, x_fast, tid, vx);
@@ -186,7 +212,7 @@ __global__ __launch_bounds__(kThreads) void wgrad_kernel(const Map mg, const Map
         const bool more = tile + 1 < tile_end; // (uniform)
         if (more) {
             tile_origin(tile + 1, W, y0, x0);
-            x_load<D>(mx, L, W, b, y0, x0, c0, x_fast, tid, vx);
+            x_load<D, PRO>(mx, ab, L, W, b, y0, x0, c0, x_fast, tid, vx);
             g_load(mg, L, W, O, b, y0, x0, o0, g_fast, tid, vg);
         }
 #pragma unroll 1
@@ -220,7 +246,7 @@ __global__ __launch_bounds__(kThreads) void wgrad_kernel(const Map mg, const Map
 #pragma unroll
         for (int i = 0; i < 16; ++i) { // C/D: column = lane & 31, row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5)
             const int o = o0 + wave * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-            if (o < O) partial[partial_index(b, slab, t, o, c, O, C, L, W)] = acc[t][i] * inv;
+            if (o < O) partial[partial_index_of(b, slab, n_slabs, t, o, c, O, C)] = acc[t][i] * inv;
         }
 }
 
@@ -259,14 +285,16 @@ __global__ __launch_bounds__(kThreads) void bias_grad_kernel(const Map mg, int B
 
 size_t scales_bytes(int B) { return ((size_t)2 * B * sizeof(unsigned) + 255) / 256 * 256; }
 
-template <int D>
-int launch_wgrad(const Map &mg, const Map &mx, const unsigned *absmax, int B, int C, int L, int W, int O, float *partial, hipStream_t s)
+template <int D, bool PRO = false>
+int launch_wgrad(const Map &mg, const Map &mx, const float *a, const float *b, const unsigned *absmax, int B, int C, int L, int W, int O, int n_slabs,
+                 float *partial, hipStream_t s)
 {
     static DynamicLds lds; // (vfa_conv.h: once per device)
-    const int status = lds.allow((const void *)wgrad_kernel<D>, Grad<D>::kLdsBytes);
+    constexpr int lds_bytes = PRO ? Grad<D>::kLdsBytesPro : Grad<D>::kLdsBytes;
+    const int status = lds.allow((const void *)wgrad_kernel<D, PRO>, lds_bytes);
     if (status != 0) return status;
-    const dim3 grid((unsigned)slabs(L, W), (unsigned)(((O + kTileO - 1) / kTileO) * (C / kTileC)), (unsigned)B);
-    hipLaunchKernelGGL(wgrad_kernel<D>, grid, dim3(kThreads), Grad<D>::kLdsBytes, s, mg, mx, absmax, B, C, L, W, O, partial);
+    const dim3 grid((unsigned)n_slabs, (unsigned)(((O + kTileO - 1) / kTileO) * (C / kTileC)), (unsigned)B);
+    hipLaunchKernelGGL((wgrad_kernel<D, PRO>), grid, dim3(kThreads), lds_bytes, s, mg, mx, a, b, absmax, B, C, L, W, O, partial);
     return (int)hipGetLastError();
 }
 
@@ -280,14 +308,20 @@ bool sizes_ok(int B, int O, int C, int L, int W)
 
 extern "C" {
 
-size_t vfa_conv3x3_wgrad_workspace_bytes(int B, int O, int C, int L, int W)
+// 0: no such problem, or an empty one
+static size_t wgrad_workspace_bytes(int B, int O, int C, int L, int W, bool trunk)
 {
     if (B <= 0 || O < 1 || C < 1 || L <= 0 || W <= 0 || O % 32 != 0 || C % kTileC != 0 || !sizes_ok(B, O, C, L, W)) return 0;
-    return scales_bytes(B) + (size_t)B * slabs(L, W) * partial_floats(O, C) * sizeof(float);
+    return scales_bytes(B) + (size_t)B * (trunk ? slabs_for(L, W, O, C) : slabs(L, W)) * partial_floats(O, C) * sizeof(float);
 }
 
-int vfa_conv3x3_wgrad_f32(const float *g, const long long *g_stride, const float *x, const long long *x_stride, int B, int C, int L, int W,
-                          int O, int dilation, float *dw, float *db, void *workspace, size_t workspace_bytes, void *stream)
+size_t vfa_conv3x3_wgrad_workspace_bytes(int B, int O, int C, int L, int W) { return wgrad_workspace_bytes(B, O, C, L, W, false); }
+
+size_t vfa_trunk_conv_wgrad_workspace_bytes(int B, int O, int C, int L, int W) { return wgrad_workspace_bytes(B, O, C, L, W, true); }
+
+// the entry points' common body; a, b: both nullptr, or the (B, C) prologue of x (dilation 1); trunk: the slabs of slabs_for
+static int wgrad(const float *g, const long long *g_stride, const float *x, const long long *x_stride, const float *a, const float *b, int B, int C,
+                 int L, int W, int O, int dilation, bool trunk, float *dw, float *db, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (B < 0 || C < 1 || L < 0 || W < 0 || O < 1 || dilation < 1 || !dw) return VFA_ERR_BAD_ARGUMENT;
     if (O % 32 != 0 || C % kTileC != 0 || dilation > kMaxDilation || !sizes_ok(B, O, C, L, W)) return VFA_ERR_UNSUPPORTED;
@@ -300,27 +334,42 @@ int vfa_conv3x3_wgrad_f32(const float *g, const long long *g_stride, const float
     if (!g || !g_stride || !x || !x_stride) return VFA_ERR_BAD_ARGUMENT;
     for (int i = 0; i < 4; ++i)
         if (g_stride[i] < 0 || x_stride[i] < 0) return VFA_ERR_BAD_ARGUMENT;
-    if (!workspace || ((uintptr_t)workspace & 15) != 0 || workspace_bytes < vfa_conv3x3_wgrad_workspace_bytes(B, O, C, L, W))
-        return VFA_ERR_BAD_ARGUMENT;
+    if (!workspace || ((uintptr_t)workspace & 15) != 0 || workspace_bytes < wgrad_workspace_bytes(B, O, C, L, W, trunk)) return VFA_ERR_BAD_ARGUMENT;
+    const int n_slabs = trunk ? slabs_for(L, W, O, C) : slabs(L, W);
     const Map mg = {g, g_stride[0], g_stride[1], g_stride[2], g_stride[3]}, mx = {x, x_stride[0], x_stride[1], x_stride[2], x_stride[3]};
     unsigned *absmax = (unsigned *)workspace;
     float *partial = (float *)((unsigned char *)workspace + scales_bytes(B));
     const hipError_t e = hipMemsetAsync(absmax, 0, scales_bytes(B), s);
     if (e != hipSuccess) return (int)e;
     int status = vfa_conv::frame_absmax(g, g_stride, B, O, L, W, absmax, stream);
-    if (status == 0) status = vfa_conv::frame_absmax(x, x_stride, B, C, L, W, absmax + B, stream);
+    if (status == 0) status = vfa_conv::frame_absmax(x, x_stride, a, b, B, C, L, W, absmax + B, stream);
     if (status != 0) return status;
-    switch (dilation) {
-    case 1: status = launch_wgrad<1>(mg, mx, absmax, B, C, L, W, O, partial, s); break;
-    case 2: status = launch_wgrad<2>(mg, mx, absmax, B, C, L, W, O, partial, s); break;
-    case 3: status = launch_wgrad<3>(mg, mx, absmax, B, C, L, W, O, partial, s); break;
-    default: status = launch_wgrad<4>(mg, mx, absmax, B, C, L, W, O, partial, s); break;
-    }
+    if (a) status = launch_wgrad<1, true>(mg, mx, a, b, absmax, B, C, L, W, O, n_slabs, partial, s);
+    else
+        switch (dilation) {
+        case 1: status = launch_wgrad<1>(mg, mx, a, b, absmax, B, C, L, W, O, n_slabs, partial, s); break;
+        case 2: status = launch_wgrad<2>(mg, mx, a, b, absmax, B, C, L, W, O, n_slabs, partial, s); break;
+        case 3: status = launch_wgrad<3>(mg, mx, a, b, absmax, B, C, L, W, O, n_slabs, partial, s); break;
+        default: status = launch_wgrad<4>(mg, mx, a, b, absmax, B, C, L, W, O, n_slabs, partial, s); break;
+        }
     if (status != 0) return status;
     const size_t per = partial_floats(O, C);
-    hipLaunchKernelGGL(wgrad_merge_kernel, dim3((unsigned)((per + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, partial, B * slabs(L, W), O, C, dw);
+    hipLaunchKernelGGL(wgrad_merge_kernel, dim3((unsigned)((per + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, partial, B * n_slabs, O, C, dw);
     if (db) hipLaunchKernelGGL(bias_grad_kernel, dim3((unsigned)O), dim3(kThreads), 0, s, mg, B, L, W, db);
     return (int)hipGetLastError();
+}
+
+int vfa_conv3x3_wgrad_f32(const float *g, const long long *g_stride, const float *x, const long long *x_stride, int B, int C, int L, int W,
+                          int O, int dilation, float *dw, float *db, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return wgrad(g, g_stride, x, x_stride, nullptr, nullptr, B, C, L, W, O, dilation, false, dw, db, workspace, workspace_bytes, stream);
+}
+
+int vfa_trunk_conv_wgrad_f32(const float *g, const long long *g_stride, const float *x, const long long *x_stride, const float *a, const float *b,
+                             int B, int C, int L, int W, int O, float *dw, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if ((a == nullptr) != (b == nullptr)) return VFA_ERR_BAD_ARGUMENT;
+    return wgrad(g, g_stride, x, x_stride, a, b, B, C, L, W, O, 1, true, dw, nullptr, workspace, workspace_bytes, stream);
 }
 
 } // extern "C"

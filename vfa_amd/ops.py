@@ -1,4 +1,5 @@
-"""Functional wrappers, one per entry point of ``include/vfa_hip.h`` (no fallback; no autograd but for ``conv3x3_train``).
+"""Functional wrappers, one per entry point of ``include/vfa_hip.h`` (no fallback; no autograd but for ``conv3x3_train`` and
+``residual_block_train``).
 
 Tensors are device tensors; every call is asynchronous on the current torch HIP stream.
 """
@@ -1711,14 +1712,20 @@ def trunk_conv(x, weight, stride=1, affine=None):
         a, b = a.contiguous(), b.contiguous()
     taps = int(weight.shape[2]) * int(weight.shape[3])
     packed, nbytes = trunk_packed_weight(weight)
-    Lo, Wo = ((L - 1) // int(stride) + 1, (W - 1) // int(stride) + 1) if L and W else (0, 0)
+    return _trunk_conv_launch(x, stride_arr, packed, nbytes, a, b, (B, C, L, W, O), taps, int(stride))
+
+
+def _trunk_conv_launch(x, stride_arr, packed, nbytes, a, b, sizes, taps, stride):
+    """``vfa_trunk_conv_f32`` on checked operands and a packed weight -> (B, O, Lo, Wo) contiguous."""
+    B, C, L, W, O = sizes
+    Lo, Wo = ((L - 1) // stride + 1, (W - 1) // stride + 1) if L and W else (0, 0)
     out = torch.empty((B, O, Lo, Wo), dtype=torch.float32, device=x.device)
     if out.numel() == 0:
         return out
     ws_bytes = _lib.lib().vfa_trunk_workspace_bytes(B)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-    _launch("vfa_trunk_conv_f32", _lib.ptr(x), stride_arr, _lib.ptr(packed), nbytes, _lib.ptr(a), _lib.ptr(b), B, C, L, W, O, taps, int(stride),
-            _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(), tag=(B, C, L, W, O, taps, int(stride)))
+    _launch("vfa_trunk_conv_f32", _lib.ptr(x), stride_arr, _lib.ptr(packed), nbytes, _lib.ptr(a), _lib.ptr(b), B, C, L, W, O, taps, stride,
+            _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(), tag=(B, C, L, W, O, taps, stride))
     return out
 
 
@@ -1750,6 +1757,201 @@ def residual_join(y, affine, shortcut, shortcut_affine=None, out=None):
         _launch("vfa_residual_join_f32", _lib.ptr(y), _lib.ptr(a), _lib.ptr(b), _lib.ptr(shortcut), _lib.ptr(ra), _lib.ptr(rb), B, C, L, W,
                 _lib.ptr(out), _lib.current_stream_handle(), tag=(B, C, L, W))
     return out
+
+
+GN_MASK_PROLOGUE, GN_MASK_OUT = 0, 1     # VFA_GN_MASK_* of include/vfa_hip.h
+
+
+def _gn_operands(name, x, groups, weight, bias):
+    """What the GroupNorm wrappers ask of the shapes of a map and its parameters -> (B, C, L, W)."""
+    if x.dtype != torch.float32 or x.dim() != 4 or int(groups) < 1 or x.shape[1] % int(groups):
+        raise ValueError(f"{name}: the map must be float32 (B, C, L, W) with groups | C, got {x.dtype} {tuple(x.shape)}, groups {groups}")
+    C = x.shape[1]
+    for t in (weight, bias):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != C):
+            raise ValueError(f"{name}: weight / bias must be float32 ({C}), got {t.dtype} {tuple(t.shape)}")
+    return tuple(x.shape)
+
+
+def group_norm_stats(x, groups, weight, bias, eps):
+    """``group_norm_affine`` that also returns what a backward needs (``vfa_group_norm_stats_f32``) -> (a, b, stats): a and b the
+    bits of ``group_norm_affine``, stats (B, groups, 2) float64, the mean and ``rstd = 1 / sqrt(var + eps)`` of each (image, group).
+    The operands are read as values: no graph is recorded (``residual_block_train`` is the differentiable caller)."""
+    B, C, L, W = _gn_operands("group_norm_stats", x, groups, weight, bias)
+    if x.numel() == 0:
+        raise ValueError("group_norm_stats: an empty map has no statistics")
+    _lib.require_device(x, weight, bias)
+    x = x.detach()
+    weight = None if weight is None else weight.detach().contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    a, b = torch.empty((B, C), dtype=torch.float32, device=x.device), torch.empty((B, C), dtype=torch.float32, device=x.device)
+    stats = torch.empty((B, int(groups), 2), dtype=torch.float64, device=x.device)
+    ws_bytes = _lib.lib().vfa_group_norm_workspace_bytes(B, int(groups))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    _launch("vfa_group_norm_stats_f32", _lib.ptr(x), (ctypes.c_longlong * 4)(*x.stride()), _lib.ptr(weight), _lib.ptr(bias), float(eps), B, C,
+            L, W, int(groups), _lib.ptr(a), _lib.ptr(b), _lib.ptr(stats), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(),
+            tag=(B, C, L, W, int(groups)))
+    return a, b, stats
+
+
+def group_norm_backward(u, y, a, b, weight, stats, groups, mask_out=None, want_params=True):
+    """The backward of ``z = F.group_norm(y, groups, weight, bias)`` behind a ReLU, from the raw map y and ``u``, the gradient behind
+    that ReLU (``vfa_group_norm_backward_f32``); a, b, stats: ``group_norm_stats(y, ...)``.  Without ``mask_out`` the ReLU is the one
+    a convolution applied as it read y, ``fmaf(a, y, b) > 0`` -> (dy, dweight, dbias).  ``mask_out``: a map of y's shape whose
+    positive values are the mask -- the output of a residual join -> (dy, dz, dweight, dbias) with ``dz = u`` where the mask holds
+    and 0 elsewhere, the gradient of the shortcut.  ``want_params=False``: dweight and dbias are None and not computed.  float64 sums
+    in a fixed order, each coefficient of ``dy = p m u + q y + r`` rounded once: the same bits on every run, and an image's dy and dz
+    alone and in a batch."""
+    B, C, L, W = _gn_operands("group_norm_backward", y, groups, weight, None)
+    for name, t in (("u", u),) + ((("mask_out", mask_out),) if mask_out is not None else ()):
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, C, L, W):
+            raise ValueError(f"group_norm_backward: {name} must be float32 {(B, C, L, W)} like y, got {t.dtype} {tuple(t.shape)}")
+    for t in (a, b):
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, C):
+            raise ValueError(f"group_norm_backward: the affine is two float32 ({B}, {C}) tensors, got {t.dtype} {tuple(t.shape)}")
+    if stats.dtype != torch.float64 or tuple(stats.shape) != (B, int(groups), 2):
+        raise ValueError(f"group_norm_backward: stats must be float64 ({B}, {int(groups)}, 2), got {stats.dtype} {tuple(stats.shape)}")
+    _lib.require_device(y, u, a, b, weight, stats, mask_out)
+    y, u, a, b, stats = y.detach().contiguous(), u.detach().contiguous(), a.contiguous(), b.contiguous(), stats.contiguous()
+    mask_out = None if mask_out is None else mask_out.detach().contiguous()
+    weight = None if weight is None else weight.detach().contiguous()
+    dy = torch.empty_like(y)
+    dz = torch.empty_like(y) if mask_out is not None else None
+    dweight = torch.empty(C, dtype=torch.float32, device=y.device) if want_params else None
+    dbias = torch.empty(C, dtype=torch.float32, device=y.device) if want_params else None
+    ws_bytes = _lib.lib().vfa_group_norm_backward_workspace_bytes(B, C)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=y.device)
+    _launch("vfa_group_norm_backward_f32", _lib.ptr(y), _lib.ptr(u), _lib.ptr(a), _lib.ptr(b), _lib.ptr(mask_out), _lib.ptr(weight),
+            _lib.ptr(stats), GN_MASK_PROLOGUE if mask_out is None else GN_MASK_OUT, B, C, L, W, int(groups), _lib.ptr(dy), _lib.ptr(dz),
+            _lib.ptr(dweight), _lib.ptr(dbias), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(), tag=(B, C, L, W, int(groups)))
+    return (dy, dweight, dbias) if mask_out is None else (dy, dz, dweight, dbias)
+
+
+def _trunk_grad_operands(name, grad, weight):
+    if weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[0] % 32 or weight.shape[1] % 32:
+        raise ValueError(f"{name}: weight must be float32 (O, C, 3, 3) with O and C multiples of 32, got {weight.dtype} {tuple(weight.shape)}")
+    if grad.dtype != torch.float32 or grad.dim() != 4 or grad.shape[1] != weight.shape[0]:
+        raise ValueError(f"{name}: grad must be float32 (B, {weight.shape[0]}, L, W), got {grad.dtype} {tuple(grad.shape)}")
+    _lib.require_device(grad, weight)
+
+
+def trunk_conv_input_grad(grad, weight):
+    """dL/dx' of ``y = F.conv2d(x', weight, padding=1)`` (``trunk_conv`` at stride 1) from grad = dL/dy (B, O, L, W), read through its
+    strides: ``vfa_trunk_conv_f32`` on ``grad`` with the planes of the transposed, tap-mirrored weight, packed per call from ``weight``
+    (O, C, 3, 3) as it lies and kept nowhere -> (B, C, L, W) contiguous; two accumulator chains where O > 256.  An image gives the
+    same bits alone and in a batch."""
+    _trunk_grad_operands("trunk_conv_input_grad", grad, weight)
+    O, C = int(weight.shape[0]), int(weight.shape[1])
+    B, _, L, W = grad.shape
+    grad = grad.detach()
+    packed, nbytes = _conv3x3_pack(weight, transposed=True)
+    return _trunk_conv_launch(grad, (ctypes.c_longlong * 4)(*grad.stride()), packed, nbytes, None, None, (B, O, L, W, C), 9, 1)
+
+
+def trunk_conv_weight_grad(grad, x, affine=None):
+    """dL/dweight (O, C, 3, 3) of ``y = F.conv2d(x', weight, padding=1)`` from grad = dL/dy (B, O, L, W) and x (B, C, L, W), both read
+    through their strides (``vfa_trunk_conv_wgrad_f32``).  ``affine = (a, b)``, both (B, C): ``x' = relu(a[b, c] * x + b[b, c])``
+    applied as x is read (the zero padding is applied to ``x'``), its power-of-two scale taken after that; ``None``: ``x' = x``.  O
+    and C multiples of 32.  The kernels of ``conv3x3_weight_grad`` with the slabs of ``slabs_for`` (``csrc/vfa_conv_grad.h``): up to
+    O C = 256^2 its slabs -- and without an affine its bits --, fewer past it, so the partials of a 512 x 512 layer are a quarter of
+    what they would be.  The same bits on every run."""
+    a, b = (None, None) if affine is None else affine
+    if x.dtype != torch.float32 or x.dim() != 4 or grad.dtype != torch.float32 or grad.dim() != 4 or grad.shape[0] != x.shape[0] \
+            or grad.shape[2:] != x.shape[2:]:
+        raise ValueError(f"trunk_conv_weight_grad: grad (B, O, L, W) and x (B, C, L, W) must be float32 maps of one size, got "
+                         f"{grad.dtype} {tuple(grad.shape)} and {x.dtype} {tuple(x.shape)}")
+    B, C, L, W = x.shape
+    O = int(grad.shape[1])
+    if C % 32 or O % 32 or not C or not O:
+        raise ValueError(f"trunk_conv_weight_grad: C and O must be multiples of 32, got {C} and {O}")
+    if affine is not None:
+        if any(t.dtype != torch.float32 or tuple(t.shape) != (B, C) for t in (a, b)):
+            raise ValueError(f"trunk_conv_weight_grad: affine must be two float32 ({B}, {C}) tensors, got {tuple(a.shape)} and {tuple(b.shape)}")
+        a, b = a.contiguous(), b.contiguous()
+    _lib.require_device(grad, x, a, b)
+    grad, x = grad.detach(), x.detach()
+    dw = torch.empty((O, C, 3, 3), dtype=torch.float32, device=x.device)
+    ws_bytes = _lib.lib().vfa_trunk_conv_wgrad_workspace_bytes(B, O, C, L, W)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+    _launch("vfa_trunk_conv_wgrad_f32", _lib.ptr(grad), (ctypes.c_longlong * 4)(*grad.stride()), _lib.ptr(x), (ctypes.c_longlong * 4)(*x.stride()),
+            _lib.ptr(a), _lib.ptr(b), B, C, L, W, O, _lib.ptr(dw), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(),
+            tag=(B, C, L, W, O, affine is not None))
+    return dw
+
+
+def residual_block_workspace_bytes(B, C, L, W):
+    """The largest transient workspace of one ``residual_block_train`` step on a (B, C, L, W) map: the weight gradient's partials."""
+    return int(_lib.lib().vfa_trunk_conv_wgrad_workspace_bytes(B, C, C, L, W))
+
+
+class _ResidualBlockTrain(torch.autograd.Function):
+    """``residual_block_train``: one node for the whole identity block -- the affines are functions of y1 and y2, so smaller
+    differentiable pieces do not compose.  Three maps are kept besides the input (y1, y2 and the join); the normalised maps are
+    recomputed in prologues.  The packed planes are made per call and kept nowhere: a weight under training changes every step."""
+
+    @staticmethod
+    def forward(ctx, x, w1, g1, b1, w2, g2, b2, groups, eps):
+        B, C, L, W = x.shape
+        x = x.detach().contiguous()
+        sizes = (B, C, L, W, C)
+
+        def conv(t, w, a=None, b=None):
+            packed, nbytes = _conv3x3_pack(w)
+            return _trunk_conv_launch(t, (ctypes.c_longlong * 4)(*t.stride()), packed, nbytes, a, b, sizes, 9, 1)
+        y1 = conv(x, w1)
+        a1, c1, s1 = group_norm_stats(y1, groups, g1, b1, eps)
+        y2 = conv(y1, w2, a1, c1)
+        a2, c2, s2 = group_norm_stats(y2, groups, g2, b2, eps)
+        out = residual_join(y2, (a2, c2), x)
+        ctx.save_for_backward(x, y1, y2, out, a1, c1, s1, a2, c2, s2, w1, g1, w2, g2)
+        ctx.groups = groups
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        x, y1, y2, out, a1, c1, s1, a2, c2, s2, w1, g1, w2, g2 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dw1 = dg1 = db1 = dw2 = dg2 = db2 = dx = None
+        dy2, dz, dg2, db2 = group_norm_backward(grad, y2, a2, c2, g2, s2, ctx.groups, mask_out=out, want_params=need[5] or need[6])
+        if need[4]:
+            dw2 = trunk_conv_weight_grad(dy2, y1, (a1, c1))
+        if any(need[:4]):
+            dx1 = trunk_conv_input_grad(dy2, w2)
+            del dy2
+            dy1, dg1, db1 = group_norm_backward(dx1, y1, a1, c1, g1, s1, ctx.groups, want_params=need[2] or need[3])
+            del dx1
+            if need[1]:
+                dw1 = trunk_conv_weight_grad(dy1, x)
+            if need[0]:
+                dx = trunk_conv_input_grad(dy1, w1).add_(dz)       # one elementwise add, the convolution term first
+        return (dx, dw1, dg1 if need[2] else None, db1 if need[3] else None, dw2, dg2 if need[5] else None, db2 if need[6] else None,
+                None, None)
+
+
+def residual_block_train(x, w1, g1, b1, w2, g2, b2, groups=16, eps=1e-5):
+    """An identity residual block of the trunk with gradients, on the HIP kernels: ``relu(gn2(conv2(relu(gn1(conv1(x))))) + x)`` with
+    3 x 3 convolutions of stride 1 without bias (w1, w2: (C, C, 3, 3), C a multiple of 32) and GroupNorms of ``groups`` groups (g, b:
+    (C) weights and biases), x (B, C, L, W) float32 -> (B, C, L, W) contiguous, the bits of ``_Block.forward_hip`` under ``no_grad``.
+    ONE once-differentiable node.  Forward: ``trunk_conv``, ``group_norm_stats``, ``trunk_conv`` with the affine as its prologue,
+    ``group_norm_stats``, ``residual_join``; x, the two raw maps, the join, the affines and the statistics are saved.  Backward:
+    ``group_norm_backward`` with the join's mask (-> dy2 and the shortcut's dz), ``trunk_conv_weight_grad`` with the first affine as
+    its prologue, ``trunk_conv_input_grad``, ``group_norm_backward`` with the prologue's mask, ``trunk_conv_weight_grad``,
+    ``trunk_conv_input_grad`` + dz -- only what ``needs_input_grad`` asks for.  Fixed summation order, no float atomics: the same
+    bits on every run without ``torch.use_deterministic_algorithms``, and an image's dx alone and in a batch; no host wait, capturable."""
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] % 32 or x.numel() == 0:
+        raise ValueError(f"residual_block_train: x must be a float32 (B, C, L, W) map with values and C a multiple of 32, got {x.dtype} {tuple(x.shape)}")
+    C = int(x.shape[1])
+    if int(groups) < 1 or C % int(groups):
+        raise ValueError(f"residual_block_train: groups must divide C = {C}, got {groups}")
+    for w in (w1, w2):
+        if w.dtype != torch.float32 or tuple(w.shape) != (C, C, 3, 3):
+            raise ValueError(f"residual_block_train: a weight must be float32 ({C}, {C}, 3, 3), got {w.dtype} {tuple(w.shape)}")
+    for t in (g1, b1, g2, b2):
+        if t.dtype != torch.float32 or tuple(t.shape) != (C,):
+            raise ValueError(f"residual_block_train: a GroupNorm parameter must be float32 ({C},), got {t.dtype} {tuple(t.shape)}")
+    _lib.require_device(x, w1, g1, b1, w2, g2, b2)
+    return _ResidualBlockTrain.apply(x, w1, g1, b1, w2, g2, b2, int(groups), float(eps))
 
 
 _STEM_MAX_OUT = 64      # kMaxOut of csrc/vfa_stem.h

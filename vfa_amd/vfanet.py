@@ -25,6 +25,11 @@ ResNet trunk at inference on the HIP kernels of ``csrc/vfa_trunk.hip`` from the 
 ``trunk_stem="hip"`` (independent of ``trunk_convs``; default ``"library"``) runs the trunk's stem -- the 7 x 7 stride-2 convolution,
 GroupNorm, ReLU and the max pooling -- at inference on the HIP kernels of ``csrc/vfa_stem.hip`` (``trunk``).  With
 ``trunk_stem = trunk_convs = head_convs = "hip"`` no library convolution runs between the camera bytes and the detections.
+
+``trunk_convs_train="hip"`` (independent of both, which stay inference-only; default ``"library"``) runs the trunk's identity
+residual blocks -- stride 1, no projection: 5 of resnet18's 8, 13 of resnet34's 16 -- WITH gradients on ``ops.residual_block_train``,
+one autograd node per block that keeps three maps instead of the library's five (``csrc/vfa_trunk_grad.hip``; ``trunk``; DESIGN.md
+4.6).  The projection blocks and the stem stay the modules they are.
 """
 import glob
 import os
@@ -57,6 +62,8 @@ HEAD_CONVS_TRAIN = ("library", "hip")
 TRUNK_CONVS = ("library", "hip")
 # Who runs the trunk's stem (``VFANet.trunk_stem``, ``VFANet.trunk``)
 TRUNK_STEM = ("library", "hip")
+# Who runs the trunk's identity residual blocks where gradients are enabled (``VFANet.trunk_convs_train``, ``VFANet.trunk``)
+TRUNK_CONVS_TRAIN = ("library", "hip")
 
 
 def _find_pretrained(base):
@@ -132,6 +139,18 @@ class _Block(nn.Module):
         yd = ops.trunk_conv(x, self.downsample[0].weight, stride)
         return ops.residual_join(y2, _gn_affine(y2, self.bn2), yd, _gn_affine(yd, self.downsample[1]), out=y2)
 
+    @property
+    def is_identity(self):
+        """Stride 1 and no projection: the shortcut is x itself."""
+        return self.downsample is None and self.conv1.stride[0] == 1
+
+    def forward_train_hip(self, x):
+        """``forward`` of an identity block with gradients on ``ops.residual_block_train``: the calls of ``forward_hip`` and their
+        bits, and a backward on the HIP kernels from three kept maps."""
+        assert self.is_identity
+        return ops.residual_block_train(x, self.conv1.weight, self.bn1.weight, self.bn1.bias, self.conv2.weight, self.bn2.weight,
+                                        self.bn2.bias, self.bn1.num_groups, self.bn1.eps)
+
 
 def _gn_affine(y, gn):
     return ops.group_norm_affine(y, gn.num_groups, gn.weight, gn.bias, gn.eps)
@@ -179,6 +198,15 @@ class _Trunk(nn.Module):
             maps.append(x)
         return maps[1], maps[2], maps[3]
 
+    def stages_train_hip(self, x):
+        """``stages`` with gradients: each identity block on ``_Block.forward_train_hip``, every other block the module it is."""
+        maps = []
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for block in layer:
+                x = block.forward_train_hip(x) if block.is_identity else block(x)
+            maps.append(x)
+        return maps[1], maps[2], maps[3]
+
     def forward(self, x):
         return self.stages(self.stem(x))
 
@@ -207,6 +235,7 @@ class VFANet(nn.Module):
         self.head_convs_train = "library"  # or "hip" (``heads``, with gradients); the same kind of attribute
         self.trunk_convs = "library"  # or "hip" (``trunk``); the same kind of attribute
         self.trunk_stem = "library"  # or "hip" (``trunk``); the same kind of attribute, independent of ``trunk_convs``
+        self.trunk_convs_train = "library"  # or "hip" (``trunk``, with gradients); the same kind of attribute, independent of both
         self.input_size = getattr(args, "resize_size", None)  # (H, W) uint8 frames are resized to (train.py:209-214); None: as they are
         self.base = _Trunk(_DEPTHS[base])
         if pretrained:
@@ -244,15 +273,23 @@ class VFANet(nn.Module):
         ``trunk_stem`` names who runs the stem (``"hip"``: the kernels of ``csrc/vfa_stem.hip``, ``_Trunk.stem_hip``) and
         ``trunk_convs`` who runs ``layer1`` .. ``layer4`` (``"hip"``: the kernels of ``csrc/vfa_trunk.hip``, ``_Trunk.stages_hip``).
         ``"hip"`` holds where the model is in eval mode, gradients are off and ``x`` is a float32 CUDA tensor with at least one image;
-        anywhere else, and with both settings on ``"library"``, this is ``self.base(x)``."""
+        anywhere else, and with both settings on ``"library"``, this is ``self.base(x)``.
+        ``trunk_convs_train`` names who runs the identity residual blocks where gradients are enabled (``"hip"``: the kernels of
+        ``csrc/vfa_trunk_grad.hip``, ``_Trunk.stages_train_hip``; the stem and the projection blocks run as modules): it holds where
+        gradients are enabled and ``x`` is a float32 CUDA tensor with at least one image, in training and in eval mode alike."""
         if self.trunk_convs not in TRUNK_CONVS:
             raise ValueError(f"VFANet.trunk: trunk_convs is one of {TRUNK_CONVS}, got {self.trunk_convs!r}")
         if self.trunk_stem not in TRUNK_STEM:
             raise ValueError(f"VFANet.trunk: trunk_stem is one of {TRUNK_STEM}, got {self.trunk_stem!r}")
+        if self.trunk_convs_train not in TRUNK_CONVS_TRAIN:
+            raise ValueError(f"VFANet.trunk: trunk_convs_train is one of {TRUNK_CONVS_TRAIN}, got {self.trunk_convs_train!r}")
         if ("hip" in (self.trunk_convs, self.trunk_stem) and not self.training and not torch.is_grad_enabled() and x.is_cuda
                 and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0):
             y = self.base.stem_hip(x) if self.trunk_stem == "hip" else self.base.stem(x)
             return self.base.stages_hip(y) if self.trunk_convs == "hip" else self.base.stages(y)
+        if (self.trunk_convs_train == "hip" and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+                and x.numel() > 0):
+            return self.base.stages_train_hip(self.base.stem(x))
         return self.base(x)
 
     def laterals(self, images):
