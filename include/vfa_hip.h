@@ -1030,6 +1030,48 @@ size_t vfa_trunk_conv_wgrad_workspace_bytes(int B, int O, int C, int L, int W);
 int vfa_trunk_conv_wgrad_f32(const float *g, const long long *g_stride, const float *x, const long long *x_stride, const float *a, const float *b,
                              int B, int C, int L, int W, int O, float *dw, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- training the projection blocks of the trunk: the gradients of a stride-2 convolution (csrc/vfa_conv_grad.hip, vfa_trunk.hip) -------
+ *                         replaces the backward of a BasicBlock of resnet.py:26-57 with stride 2 and a 1 x 1 projection
+ * y = conv(x, w, stride 2) with w (O, C, 3, 3) and padding 1 (kernel 3) or w (O, C, 1, 1) without padding (kernel 1); x (B, C, L, W), y and
+ * its gradient g (B, O, Lo, Wo), Lo = (L - 1) / 2 + 1, Wo = (W - 1) / 2 + 1.  O and C multiples of 32.  float32, fixed summation order,
+ * no float atomics: the same bits on every run.  Stream-ordered, no host wait, capturable.  The integer rules: csrc/vfa_conv_grad.h.
+ *
+ * vfa_trunk_down_wgrad_f32: dw[o, c, ty, tx] = sum_b sum_(i, j) g[b, o, i, j] x[b, c, 2 i + ty - 1, 2 j + tx - 1] (kernel 1: x[b, c, 2 i, 2 j]),
+ *   positions outside x being zeros; dw (O, C, kernel, kernel) contiguous; (L, W) is the size of x; g and x are read through their
+ *   four element strides.  The kernel of vfa_conv3x3_wgrad_f32 (cells as K, the three-product fp16 split of both operands under
+ *   per-image power-of-two scales) with K tiles of 2 x 32 cells and the 5 x 65 window of x stored by column parity; float32 partials
+ *   per (image, slab) in [image][slab][tap][o][c] with slabs_for(Lo, Wo, O, C) slabs, merged in float64 in ascending order.
+ *   workspace: vfa_trunk_down_wgrad_workspace_bytes(B, O, C, L, W, kernel) = pad256(8 B) + 4 B slabs_for(Lo, Wo, O, C) kernel^2 O C
+ *   bytes, 16-byte aligned.
+ * vfa_trunk_down_dgrad_f32: dx[b, c, y, x] = sum_o sum g[b, o, i, j] w[o, c, ty, tx] over the (i, j, ty, tx) with 2 i + ty - 1 = y and
+ *   2 j + tx - 1 = x; dx (B, C, L, W) contiguous; g is read through its strides, weight (O, C, kernel, kernel) contiguous as it lies.
+ *   kernel 3: dx falls into four parity classes (y & 1, x & 1) with 1, 2, 2 and 4 taps, one launch of the dense kernel of
+ *   vfa_trunk_conv_f32 each over that class's taps alone (a class without positions is not launched), stored through doubled
+ *   strides: no zero-stuffed copy of g exists, and EVERY element of dx is written exactly once.  Two accumulator chains where
+ *   O > 256; one scale per image from the absmax of the whole of g; an image gives the same bits alone and in a batch.
+ *   accumulate 1: the stored value is dx + the sum instead, in that order -- the second term of a sum of two input gradients.
+ *   kernel 1 touches only the class (0, 0) and exists with accumulate 1 alone (accumulate 0: VFA_ERR_UNSUPPORTED).  A projection
+ *   block's dx is the 3 x 3 term FIRST (accumulate 0), then the projection's term added to it (kernel 1, accumulate 1): one rounding
+ *   of each term and one of the sum, the order fixed.
+ *   workspace: vfa_trunk_down_dgrad_workspace_bytes(B, O, C, kernel) = pad256(4 B) + 64 + 4 kernel^2 ceil(C / 128) 128 O bytes,
+ *   16-byte aligned: the scales and the packed planes, made by every call and kept nowhere.
+ *
+ * Measured on one MI355X (tools/bench_trunk_proj_train.py, resnet18, 720 x 1280, 7 | 28 images; DESIGN 4.6 has the table): against the
+ * library's gradients of the same convolutions the 3 x 3 weight gradient takes 1.5 - 2.4 x and the 1 x 1 weight gradient 1.7 - 3.3 x
+ * their time (the weak point: a workgroup stages 128 outputs of g for 32 inputs and one or nine taps), the 3 x 3 input gradient
+ * 0.63 - 1.37 x, the projection's added term 0.68 - 1.56 x.  wgrad_down_kernel<9>: 256 VGPRs + 144 AGPRs, 86 816 bytes of LDS;
+ * wgrad_down_kernel<1>: 176 + 16, 45 056; the class kernels: 82 - 200 VGPRs + 64 AGPRs, 53 248 - 59 168 bytes; scratch 0 in all.
+ *
+ * Errors, decided before anything is launched: a NULL pointer, a negative stride or size, a kernel other than 3 and 1, (Lo, Wo) that
+ * is not the stride-2 size of (L, W), a short or misaligned workspace: VFA_ERR_BAD_ARGUMENT; O or C not a multiple of 32, B or
+ * L > 65535, L * W >= 2^30: VFA_ERR_UNSUPPORTED.  B == 0 or L * W == 0: dw is zeros, dx is not written. */
+size_t vfa_trunk_down_wgrad_workspace_bytes(int B, int O, int C, int L, int W, int kernel);
+int vfa_trunk_down_wgrad_f32(const float *g, const long long *g_stride, const float *x, const long long *x_stride, int B, int C, int L, int W, int O,
+                             int kernel, float *dw, void *workspace, size_t workspace_bytes, void *stream);
+size_t vfa_trunk_down_dgrad_workspace_bytes(int B, int O, int C, int kernel);
+int vfa_trunk_down_dgrad_f32(const float *g, const long long *g_stride, const float *weight, int B, int O, int Lo, int Wo, int C, int L, int W,
+                             int kernel, int accumulate, float *dx, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- the stem of the ResNet trunk at inference (csrc/vfa_stem.hip; the integer rules: csrc/vfa_stem.h) ------------------------------
  *                         replaces conv1 and the max pooling of resnet.py:100-102, 139-140 in eval mode
  * float32; fixed summation order and no atomics: the same bits on every run, and an image gives the same bits alone and in a

@@ -166,6 +166,10 @@ SIGNATURES = {
                                     _c_size_t, _vp],
     "vfa_trunk_conv_wgrad_workspace_bytes": [_c_int, _c_int, _c_int, _c_int, _c_int],
     "vfa_trunk_conv_wgrad_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_size_t, _vp],
+    "vfa_trunk_down_wgrad_workspace_bytes": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int],
+    "vfa_trunk_down_wgrad_f32": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_size_t, _vp],
+    "vfa_trunk_down_dgrad_workspace_bytes": [_c_int, _c_int, _c_int, _c_int],
+    "vfa_trunk_down_dgrad_f32": [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_size_t, _vp],
 }
 
 _lib = None

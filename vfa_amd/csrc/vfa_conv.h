@@ -3,6 +3,8 @@
 // the tile's staged window, which window positions are inside the map (the others are the zero padding), and where a weight sits in
 // the packed planes.  One rule in (taps, s, d): taps 9 (3 x 3, zero padding d) or 1 (1 x 1, no padding), stride s, dilation d;
 // valid() names the combinations that exist -- the heads (vfa_conv.hip) are (9, 1, 1..4), the trunk (vfa_trunk.hip) (9 | 1, 1 | 2, 1).
+// A third family, the BLOCKS 10 r + c (11, 12, 21, 22; stride 1, no padding): r x c taps that reach down and right, tap t = c dy + dx
+// reading map position (y + dy, x + dx) -- the four parity classes of a stride-2 convolution's input gradient (vfa_conv_grad.h).
 //
 // The output is (Lo, Wo) = (out_size(L, s), out_size(W, s)).  A tile is kTileRows x kTileCols OUTPUT cells of one frame and kTileOut
 // outputs; the output cell (ry, rx) of the tile at (y0, x0) is output position (y0 + ry, x0 + rx).
@@ -10,6 +12,8 @@
 //       position (s y0 - d + wy, s x0 - d + wx); tap t = 3 ty + tx of the cell (ry, rx) reads window position (s ry + ty d, s rx + tx d):
 //       map position (s y + (ty - 1) d, s x + (tx - 1) d).
 //   taps 1: the window is the tile itself, window position (wy, wx) being map position (s (y0 + wy), s (x0 + wx)).
+//   block r x c: the window is (kTileRows + r - 1) x (kTileCols + c - 1) positions from map position (y0, x0); tap t of the cell
+//       (ry, rx) reads window position (ry + t / c, rx + t % c).
 // Where a window position lies in LDS is its LOCATION.  At stride 1 (and with one tap) location = wy cols + wx.  At stride 2 the even
 // window columns of a row come first and the odd ones behind them: the 32 cells of an MFMA operand read tap tx at the columns
 // 2 rx + tx, which are 32 CONSECUTIVE locations of one half (tx = 0: even rx; tx = 1: odd rx; tx = 2: even rx + 1), so their 80-byte
@@ -49,12 +53,21 @@ VFA_CONV_HD bool valid(int taps, int s, int d)
     if (taps == 9) return s == 1 ? d >= 1 && d <= kMaxDilation : s == 2 && d == 1;
     return taps == 1 && (s == 1 || s == 2) && d == 1;
 }
+// the blocks of taps and how many taps a code has (9 and 1 are their own count)
+VFA_CONV_HD constexpr bool is_block(int taps) { return taps == 11 || taps == 12 || taps == 21 || taps == 22; }
+VFA_CONV_HD constexpr int tap_count(int taps) { return is_block(taps) ? (taps / 10) * (taps % 10) : taps; }
 VFA_CONV_HD int out_size(int n, int s) { return n < 1 ? 0 : (n - 1) / s + 1; }
 VFA_CONV_HD int tiles_x(int Wo) { return (Wo + kTileCols - 1) / kTileCols; }
 VFA_CONV_HD int tiles_y(int Lo) { return (Lo + kTileRows - 1) / kTileRows; }
 VFA_CONV_HD int out_tiles(int O) { return (O + kTileOut - 1) / kTileOut; }
-VFA_CONV_HD constexpr int window_rows(int taps, int s, int d) { return taps == 9 ? s * (kTileRows - 1) + 2 * d + 1 : kTileRows; }
-VFA_CONV_HD constexpr int window_cols(int taps, int s, int d) { return taps == 9 ? s * (kTileCols - 1) + 2 * d + 1 : kTileCols; }
+VFA_CONV_HD constexpr int window_rows(int taps, int s, int d)
+{
+    return taps == 9 ? s * (kTileRows - 1) + 2 * d + 1 : is_block(taps) ? kTileRows + taps / 10 - 1 : kTileRows;
+}
+VFA_CONV_HD constexpr int window_cols(int taps, int s, int d)
+{
+    return taps == 9 ? s * (kTileCols - 1) + 2 * d + 1 : is_block(taps) ? kTileCols + taps % 10 - 1 : kTileCols;
+}
 VFA_CONV_HD constexpr int window_locations(int taps, int s, int d) { return window_rows(taps, s, d) * window_cols(taps, s, d); }
 // chunks of the first accumulator chain (all of them up to kSplitC channels)
 VFA_CONV_HD int first_chunks(int C) { return C > kSplitC ? (C / kChunkC + 1) / 2 : C / kChunkC; }
@@ -79,6 +92,7 @@ VFA_CONV_HD int window_location(int wy, int wx, int taps, int s, int d)
 VFA_CONV_HD int tap_location(int ry, int rx, int t, int taps, int s, int d)
 {
     if (taps == 1) return window_location(ry, rx, taps, s, d);
+    if (is_block(taps)) return window_location(ry + t / (taps % 10), rx + t % (taps % 10), taps, s, d);
     return window_location(s * ry + (t / 3) * d, s * rx + (t % 3) * d, taps, s, d);
 }
 

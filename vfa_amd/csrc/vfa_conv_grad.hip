@@ -24,6 +24,9 @@
 //   3. wgrad_merge_kernel: per element of dW the partials in ascending (frame, slab) order, summed in float64, rounded once.
 //   4. bias_grad_kernel: per output a workgroup; thread i sums the cells i, i + 256, .. of frame 0, then of frame 1, .. in float64,
 //      the 256 sums are merged in a fixed tree and rounded once.
+//   5. wgrad_down_kernel<9 | 1> (vfa_trunk_down_wgrad_f32): the weight gradient of the trunk's stride-2 convolutions, 3 x 3 with
+//      padding 1 and 1 x 1: wgrad_kernel on K tiles of 2 x 32 cells of g, whose 5 x 65 window of x is stored by column parity so that
+//      a tap still only moves an offset of the transposed reads; partials with 9 or 1 planes, merged by wgrad_merge_kernel<9 | 1>.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -69,11 +72,11 @@ template <int D> __device__ __forceinline__ void x_quad_of(int e, bool chan_fast
     if (chan_fast) { c4 = e & 7; loc = e >> 3; }
     else { c4 = e / Grad<D>::kLoc; loc = e - c4 * Grad<D>::kLoc; }
 }
-// quad e of the tile of g: (cell of the tile, four outputs)
-__device__ __forceinline__ void g_quad_of(int e, bool chan_fast, int &cell, int &c4)
+// quad e of the tile of g: (cell of the tile, four outputs); CELLS: the cells of the tile, whole rows of it
+template <int CELLS = kTileCells> __device__ __forceinline__ void g_quad_of(int e, bool chan_fast, int &cell, int &c4)
 {
     if (chan_fast) { c4 = e & (kTileO / 4 - 1); cell = e / (kTileO / 4); }
-    else { c4 = e / kTileCells; cell = e & (kTileCells - 1); }
+    else { c4 = e / CELLS; cell = e & (CELLS - 1); }
 }
 
 __device__ __forceinline__ float prologue(float a, float x, float b)
@@ -122,12 +125,14 @@ __device__ __forceinline__ void x_store(_Float16 *x_hi, _Float16 *x_lo, float sx
 }
 
 // the tile's cells of g: outputs o0 .. o0 + 127; a cell outside the map and an output past O are zeros
-__device__ __forceinline__ void g_load(const Map m, int L, int W, int O, int b, int y0, int x0, int o0, bool chan_fast, int tid, float (&v)[kGLoads][4])
+template <int CELLS = kTileCells>
+__device__ __forceinline__ void g_load(const Map m, int L, int W, int O, int b, int y0, int x0, int o0, bool chan_fast, int tid,
+                                       float (&v)[kGLoads * CELLS / kTileCells][4])
 {
 #pragma unroll
-    for (int j = 0; j < kGLoads; ++j) {
+    for (int j = 0; j < kGLoads * CELLS / kTileCells; ++j) {
         int cell, c4;
-        g_quad_of(tid + kThreads * j, chan_fast, cell, c4);
+        g_quad_of<CELLS>(tid + kThreads * j, chan_fast, cell, c4);
         const int y = y0 + cell / kTileCols, x = x0 + cell % kTileCols, o = o0 + 4 * c4;
         const bool ok = y < L && x < W && o < O; // (O % 4 == 0: a quad is inside or outside)
         const float *p = m.x + (ok ? b * m.s_frame + (long long)o * m.s_chan + y * m.s_row + x * m.s_col : 0);
@@ -136,12 +141,13 @@ __device__ __forceinline__ void g_load(const Map m, int L, int W, int O, int b, 
     }
 }
 
-__device__ __forceinline__ void g_store(_Float16 *g_hi, _Float16 *g_lo, float sg, bool chan_fast, int tid, const float (&v)[kGLoads][4])
+template <int CELLS = kTileCells>
+__device__ __forceinline__ void g_store(_Float16 *g_hi, _Float16 *g_lo, float sg, bool chan_fast, int tid, const float (&v)[kGLoads * CELLS / kTileCells][4])
 {
 #pragma unroll
-    for (int j = 0; j < kGLoads; ++j) {
+    for (int j = 0; j < kGLoads * CELLS / kTileCells; ++j) {
         int cell, c4;
-        g_quad_of(tid + kThreads * j, chan_fast, cell, c4);
+        g_quad_of<CELLS>(tid + kThreads * j, chan_fast, cell, c4);
         uint2 hi, lo;
         vfa_dev::split_f16x4(v[j][0] * sg, v[j][1] * sg, v[j][2] * sg, v[j][3] * sg, hi, lo);
         *(uint2 *)(g_hi + cell * kGHalves + 4 * c4) = hi;
@@ -250,15 +256,153 @@ __global__ __launch_bounds__(kThreads) void wgrad_kernel(const Map mg, const Map
         }
 }
 
+// ---- stride 2 (vfa_trunk_down_wgrad_f32; the rules: vfa_conv_grad.h) -------------------------------------------------------------------
+// TAPS 9: the 3 x 3 weight with padding 1; TAPS 1: the 1 x 1 weight.  g is (Lo, Wo), x (L, W).  wgrad_kernel with K tiles of 2 x 32
+// cells (64 cells of g, a 5 x 65 window of x stored by column parity: 52 000 + 34 816 bytes), two per tile of the slab walk.
+template <int TAPS> struct Down {
+    static constexpr int kCells = kDownRows * kTileCols;
+    static constexpr int kLoc = down_window_locations(TAPS);
+    static constexpr int kQuads = kLoc * (kTileC / 4);
+    static constexpr int kLoads = (kQuads + kThreads - 1) / kThreads;
+    static constexpr int kGLoadsDown = kGLoads * kCells / kTileCells;
+    static constexpr int kPlaneHalves = kLoc * kLocHalves;
+    static constexpr int kGPlaneHalvesDown = kCells * kGHalves;
+    static constexpr int kLdsBytes = (2 * kPlaneHalves + 2 * kGPlaneHalvesDown) * 2;
+    static_assert(kCells % 16 == 0 && kGQuads % kThreads == 0 && (kCells * (kTileO / 4)) % kThreads == 0, "whole steps, whole loads");
+    static_assert(kLdsBytes <= 160 * 1024, "the window of x and the cells of g of one K tile share the CU's LDS");
+};
+
+// quad e of the K tile's window: (window position in map order, four inputs)
+template <int TAPS> __device__ __forceinline__ void down_quad_of(int e, bool chan_fast, int &p, int &c4)
+{
+    if (chan_fast) { c4 = e & 7; p = e >> 3; }
+    else { c4 = e / Down<TAPS>::kLoc; p = e - c4 * Down<TAPS>::kLoc; }
+}
+
+template <int TAPS>
+__device__ __forceinline__ void down_x_load(const Map m, int L, int W, int b, int y0, int x0, int c0, bool chan_fast, int tid,
+                                            float (&v)[Down<TAPS>::kLoads][4])
+{
+#pragma unroll
+    for (int j = 0; j < Down<TAPS>::kLoads; ++j) {
+        const int e = tid + kThreads * j;
+        int p, c4, y, x;
+        down_quad_of<TAPS>(e, chan_fast, p, c4);
+        const bool ok = e < Down<TAPS>::kQuads && down_window_position(p, y0, x0, TAPS, L, W, y, x);
+        const float *src = m.x + (ok ? b * m.s_frame + (long long)(c0 + 4 * c4) * m.s_chan + y * m.s_row + x * m.s_col : 0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[j][k] = ok ? src[k * m.s_chan] : 0.0f;
+    }
+}
+
+template <int TAPS>
+__device__ __forceinline__ void down_x_store(_Float16 *x_hi, _Float16 *x_lo, float sx, bool chan_fast, int tid, const float (&v)[Down<TAPS>::kLoads][4])
+{
+#pragma unroll
+    for (int j = 0; j < Down<TAPS>::kLoads; ++j) {
+        const int e = tid + kThreads * j;
+        int p, c4;
+        down_quad_of<TAPS>(e, chan_fast, p, c4);
+        uint2 hi, lo;
+        vfa_dev::split_f16x4(v[j][0] * sx, v[j][1] * sx, v[j][2] * sx, v[j][3] * sx, hi, lo);
+        if (e < Down<TAPS>::kQuads) {
+            const int loc = down_window_location(p, TAPS);
+            *(uint2 *)(x_hi + loc * kLocHalves + 4 * c4) = hi;
+            *(uint2 *)(x_lo + loc * kLocHalves + 4 * c4) = lo;
+        }
+    }
+}
+
+// grid (slabs of (Lo, Wo), output tiles x input chunks, frames), as wgrad_kernel
+template <int TAPS>
+__global__ __launch_bounds__(kThreads) void wgrad_down_kernel(const Map mg, const Map mx, const unsigned *__restrict__ absmax, int B, int C, int L, int W,
+                                                              int Lo, int Wo, int O, float *__restrict__ partial)
+{
+    typedef Down<TAPS> DN;
+    extern __shared__ __align__(16) unsigned char lds[];
+    _Float16 *x_hi = (_Float16 *)lds, *x_lo = x_hi + DN::kPlaneHalves, *g_hi = x_lo + DN::kPlaneHalves, *g_lo = g_hi + DN::kGPlaneHalvesDown;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int slab = blockIdx.x, b = blockIdx.z, n_c = C / kTileC;
+    const int o0 = ((int)blockIdx.y / n_c) * kTileO, c0 = ((int)blockIdx.y % n_c) * kTileC;
+    const bool g_fast = mg.s_chan == 1, x_fast = mx.s_chan == 1;
+    const int eg = vfa_dev::split_exponent(absmax[b], kExp), ex = vfa_dev::split_exponent(absmax[B + b], kExp);
+    const float sg = vfa_dev::pow2f(eg), sx = vfa_dev::pow2f(ex);
+    const int n_slabs = (int)gridDim.x; // slabs_for(Lo, Wo, O, C)
+    const int k_begin = slab_begin_of(slab, n_slabs, Lo, Wo) * kDownHalves, k_end = slab_begin_of(slab + 1, n_slabs, Lo, Wo) * kDownHalves;
+
+    const int q = (lane >> 2) & 3, p = lane & 3, half16 = (lane >> 4) & 1; // (the transposed reads: wgrad_kernel)
+    const int k_lane = 8 * h + q, ch_lane = 16 * half16 + 4 * p;
+
+    float vx[DN::kLoads][4], vg[DN::kGLoadsDown][4];
+    int y0, x0;
+    down_origin(k_begin / kDownHalves, k_begin % kDownHalves, Wo, y0, x0);
+    down_x_load<TAPS>(mx, L, W, b, y0, x0, c0, x_fast, tid, vx);
+    g_load<DN::kCells>(mg, Lo, Wo, O, b, y0, x0, o0, g_fast, tid, vg);
+    vfa_dev::fp16_saturate_mode(true);
+    down_x_store<TAPS>(x_hi, x_lo, sx, x_fast, tid, vx);
+    g_store<DN::kCells>(g_hi, g_lo, sg, g_fast, tid, vg);
+    vfa_dev::fp16_saturate_mode(false);
+    __syncthreads();
+
+    f32x16 acc[TAPS];
+#pragma unroll
+    for (int t = 0; t < TAPS; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+
+    for (int k = k_begin; k < k_end; ++k) { // K tiles: ascending tiles, the upper half of a tile first
+        const bool more = k + 1 < k_end; // (uniform)
+        if (more) {
+            down_origin((k + 1) / kDownHalves, (k + 1) % kDownHalves, Wo, y0, x0);
+            down_x_load<TAPS>(mx, L, W, b, y0, x0, c0, x_fast, tid, vx);
+            g_load<DN::kCells>(mg, Lo, Wo, O, b, y0, x0, o0, g_fast, tid, vg);
+        }
+#pragma unroll 1
+        for (int ks = 0; ks < DN::kCells / 16; ++ks) { // 16 cells of one row of the K tile
+            const int ry = ks >> 1, rx = (ks & 1) * 16 + k_lane;
+            const int g_at = (ry * kTileCols + rx) * kGHalves + wave * 32 + ch_lane;
+            const f16x8 gh = operand(g_hi + g_at, kGHalves), gl = operand(g_lo + g_at, kGHalves);
+#pragma unroll
+            for (int t = 0; t < TAPS; ++t) {
+                const int x_at = down_tap_location(ry, rx, t, TAPS) * kLocHalves + ch_lane;
+                const f16x8 xh = operand(x_hi + x_at, kLocHalves), xl = operand(x_lo + x_at, kLocHalves);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gl, xh, acc[t], 0, 0, 0); // rows = outputs, columns = inputs
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gh, xh, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gh, xl, acc[t], 0, 0, 0);
+            }
+        }
+        __syncthreads(); // the planes are free
+        if (more) {
+            vfa_dev::fp16_saturate_mode(true);
+            down_x_store<TAPS>(x_hi, x_lo, sx, x_fast, tid, vx);
+            g_store<DN::kCells>(g_hi, g_lo, sg, g_fast, tid, vg);
+            vfa_dev::fp16_saturate_mode(false);
+            __syncthreads();
+        }
+    }
+
+    const float inv = vfa_dev::pow2f(-(eg + ex));
+    const int c = c0 + r;
+#pragma unroll
+    for (int t = 0; t < TAPS; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { // C/D: column = lane & 31, row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5)
+            const int o = o0 + wave * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+            if (o < O) partial[down_partial_index(b, slab, n_slabs, t, o, c, O, C, TAPS)] = acc[t][i] * inv;
+        }
+}
+
 // one thread per element (t, o, c) of a partial: consecutive threads on consecutive addresses of every partial
+template <int TAPS = kTaps>
 __global__ __launch_bounds__(kThreads) void wgrad_merge_kernel(const float *__restrict__ partial, int n_partials, int O, int C, float *__restrict__ dw)
 {
-    const size_t per = partial_floats(O, C), i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    const size_t per = down_partial_floats(O, C, TAPS), i = (size_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= per) return;
     double sum = 0.0;
     for (int k = 0; k < n_partials; ++k) sum += (double)partial[(size_t)k * per + i]; // ascending (frame, slab)
     const size_t oc = i % ((size_t)O * C), t = i / ((size_t)O * C);
-    dw[oc * kTaps + t] = (float)sum;
+    dw[oc * TAPS + t] = (float)sum;
 }
 
 // grid (O): thread i takes the cells i, i + 256, .. of frame 0, then of frame 1, ..
@@ -302,6 +446,21 @@ bool sizes_ok(int B, int O, int C, int L, int W)
 {
     return B <= 65535 && L <= 65535 && (long long)L * W <= INT32_MAX / 2 && (long long)O * C * kTaps <= INT32_MAX / 2 &&
            (long long)((O + kTileO - 1) / kTileO) * (C / kTileC) <= 65535;
+}
+
+template <int TAPS>
+int launch_wgrad_down(const Map &mg, const Map &mx, const unsigned *absmax, int B, int C, int L, int W, int O, int n_slabs, float *partial,
+                             float *dw, hipStream_t s)
+{
+    static DynamicLds lds; // (vfa_conv.h: once per device)
+    const int status = lds.allow((const void *)wgrad_down_kernel<TAPS>, Down<TAPS>::kLdsBytes);
+    if (status != 0) return status;
+    const int Lo = out_size(L, 2), Wo = out_size(W, 2);
+    const dim3 grid((unsigned)n_slabs, (unsigned)(((O + kTileO - 1) / kTileO) * (C / kTileC)), (unsigned)B);
+    hipLaunchKernelGGL((wgrad_down_kernel<TAPS>), grid, dim3(kThreads), Down<TAPS>::kLdsBytes, s, mg, mx, absmax, B, C, L, W, Lo, Wo, O, partial);
+    const size_t per = down_partial_floats(O, C, TAPS);
+    hipLaunchKernelGGL(wgrad_merge_kernel<TAPS>, dim3((unsigned)((per + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, partial, B * n_slabs, O, C, dw);
+    return (int)hipGetLastError();
 }
 
 } // namespace
@@ -354,7 +513,7 @@ static int wgrad(const float *g, const long long *g_stride, const float *x, cons
         }
     if (status != 0) return status;
     const size_t per = partial_floats(O, C);
-    hipLaunchKernelGGL(wgrad_merge_kernel, dim3((unsigned)((per + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, partial, B * n_slabs, O, C, dw);
+    hipLaunchKernelGGL(wgrad_merge_kernel<kTaps>, dim3((unsigned)((per + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, partial, B * n_slabs, O, C, dw);
     if (db) hipLaunchKernelGGL(bias_grad_kernel, dim3((unsigned)O), dim3(kThreads), 0, s, mg, B, L, W, db);
     return (int)hipGetLastError();
 }
@@ -370,6 +529,38 @@ int vfa_trunk_conv_wgrad_f32(const float *g, const long long *g_stride, const fl
 {
     if ((a == nullptr) != (b == nullptr)) return VFA_ERR_BAD_ARGUMENT;
     return wgrad(g, g_stride, x, x_stride, a, b, B, C, L, W, O, 1, true, dw, nullptr, workspace, workspace_bytes, stream);
+}
+
+// (L, W): the size of x; kernel 3 | 1.  0: no such problem, or an empty one
+size_t vfa_trunk_down_wgrad_workspace_bytes(int B, int O, int C, int L, int W, int kernel)
+{
+    if (B <= 0 || O < 1 || C < 1 || L <= 0 || W <= 0 || (kernel != 3 && kernel != 1) || O % 32 != 0 || C % kTileC != 0 || !sizes_ok(B, O, C, L, W)) return 0;
+    return scales_bytes(B) + (size_t)B * slabs_for(out_size(L, 2), out_size(W, 2), O, C) * down_partial_floats(O, C, kernel * kernel) * sizeof(float);
+}
+
+int vfa_trunk_down_wgrad_f32(const float *g, const long long *g_stride, const float *x, const long long *x_stride, int B, int C, int L, int W, int O,
+                             int kernel, float *dw, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (B < 0 || C < 1 || L < 0 || W < 0 || O < 1 || (kernel != 3 && kernel != 1) || !dw) return VFA_ERR_BAD_ARGUMENT;
+    if (O % 32 != 0 || C % kTileC != 0 || !sizes_ok(B, O, C, L, W)) return VFA_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    if (B == 0 || (long long)L * W == 0) return (int)hipMemsetAsync(dw, 0, (size_t)O * C * kernel * kernel * sizeof(float), s); // an empty sum
+    if (!g || !g_stride || !x || !x_stride) return VFA_ERR_BAD_ARGUMENT;
+    for (int i = 0; i < 4; ++i)
+        if (g_stride[i] < 0 || x_stride[i] < 0) return VFA_ERR_BAD_ARGUMENT;
+    if (!workspace || ((uintptr_t)workspace & 15) != 0 || workspace_bytes < vfa_trunk_down_wgrad_workspace_bytes(B, O, C, L, W, kernel))
+        return VFA_ERR_BAD_ARGUMENT;
+    const int Lo = out_size(L, 2), Wo = out_size(W, 2), n_slabs = slabs_for(Lo, Wo, O, C);
+    const Map mg = {g, g_stride[0], g_stride[1], g_stride[2], g_stride[3]}, mx = {x, x_stride[0], x_stride[1], x_stride[2], x_stride[3]};
+    unsigned *absmax = (unsigned *)workspace;
+    float *partial = (float *)((unsigned char *)workspace + scales_bytes(B));
+    const hipError_t e = hipMemsetAsync(absmax, 0, scales_bytes(B), s);
+    if (e != hipSuccess) return (int)e;
+    int status = vfa_conv::frame_absmax(g, g_stride, B, O, Lo, Wo, absmax, stream);
+    if (status == 0) status = vfa_conv::frame_absmax(x, x_stride, B, C, L, W, absmax + B, stream); // (1 x 1: a scale of the whole of x serves)
+    if (status != 0) return status;
+    return kernel == 3 ? launch_wgrad_down<9>(mg, mx, absmax, B, C, L, W, O, n_slabs, partial, dw, s)
+                       : launch_wgrad_down<1>(mg, mx, absmax, B, C, L, W, O, n_slabs, partial, dw, s);
 }
 
 } // extern "C"

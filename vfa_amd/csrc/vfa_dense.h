@@ -26,12 +26,16 @@
 //      are added once in fp32, first + second: the rounding error grows with the length of an fp32 chain.
 //      Epi: what becomes of v = sum 2^-(ea + ew), stored as MFMA rows (32 consecutive floats of an NCHW row): EpiRaw stores v,
 //      EpiAffine act(fmaf(v, scale[o] | 1, shift[o] | 0)).  Its per-output part is read once per output, outside the cell rows.
+//      Epi::at says where an element goes: contiguous (B, O, Lo, Wo), or (EpiDown) every other row and column of a larger map.
+//      TAPS may also be a BLOCK of taps (vfa_conv.h: 11, 21, 12, 22), whose slices are a run of the nine of a nine-tap pack: the
+//      parity classes of a stride-2 convolution's input gradient (vfa_conv_grad.h, vfa_trunk.hip).
 #ifndef VFA_DENSE_H
 #define VFA_DENSE_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "vfa_conv.h"
+#include "vfa_conv_grad.h"
 #include "vfa_hip.h"
 #include "vfa_split.h"
 
@@ -132,8 +136,10 @@ inline void launch_absmax(const Map &m, const float *a, const float *b, int Lv, 
     hipLaunchKernelGGL(absmax_kernel, grid, dim3(kThreads), 0, s, m, a, b, Lv, Wv, step, absmax);
 }
 
-// one thread per four channels of one (output, tap): both pieces.  transposed: `weight` is (C, O, 3, 3) and the planes are those of
-// its transposed, tap-mirrored form w'[o, c, t] = weight[c, o, taps - 1 - t], the weight of the convolution's input gradient
+// one thread per four channels of one (output, tap): both pieces.  transposed 1: `weight` is (C, O, 3, 3) and the planes are those of
+// its transposed, tap-mirrored form w'[o, c, t] = weight[c, o, taps - 1 - t], the weight of the convolution's input gradient;
+// transposed 2 (taps 9): w'[o, c, t] = weight[c, o, down_source_tap(t)], the four class blocks of a stride-2 convolution's input
+// gradient behind one another (vfa_conv_grad.h)
 __global__ __launch_bounds__(kThreads) void pack_kernel(const float *__restrict__ weight, int O, int C, int taps, int transposed,
                                                         unsigned char *__restrict__ packed)
 {
@@ -155,7 +161,8 @@ __global__ __launch_bounds__(kThreads) void pack_kernel(const float *__restrict_
     if (o < O) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            v[j] = (transposed ? weight[((size_t)(c + j) * O + o) * taps + (taps - 1 - t)] : weight[((size_t)o * C + c + j) * taps + t]) * sw;
+            v[j] = (transposed ? weight[((size_t)(c + j) * O + o) * taps + (transposed == 2 ? vfa_conv_grad::down_source_tap(t) : taps - 1 - t)]
+                               : weight[((size_t)o * C + c + j) * taps + t]) * sw;
     }
     uint2 hi, lo;
     vfa_dev::fp16_saturate_mode(true);
@@ -205,20 +212,38 @@ inline size_t scales_workspace_bytes(int B) { return B <= 0 ? 0 : ((size_t)B * s
 
 // ---- the epilogues: output(o) once per output channel, then (per-output part, v = sum 2^-(ea + ew)) -> the stored value ----------
 
+// at(): where element (b, o, y, x) of the (B, O, Lo, Wo) result is stored
+__device__ __forceinline__ size_t contiguous_at(int b, int o, int y, int x, int O, int Lo, int Wo) { return (((size_t)b * O + o) * Lo + y) * Wo + x; }
+
 struct EpiRaw { // the raw convolution
     struct Out {};
+    __device__ __forceinline__ size_t at(int b, int o, int y, int x, int O, int Lo, int Wo) const { return contiguous_at(b, o, y, x, O, Lo, Wo); }
     __device__ __forceinline__ Out output(int) const { return {}; }
-    __device__ __forceinline__ float operator()(Out, float v) const { return v; }
+    __device__ __forceinline__ float operator()(Out, float v, const float *) const { return v; }
+};
+
+// a parity class of a stride-2 convolution's input gradient: cell (y, x) of the class is position (2 y + py, 2 x + px) of the
+// contiguous (B, O, L, W) gradient; add: the stored value is what lies there + v, in that order (the second term of a sum)
+struct EpiDown {
+    int L, W, py, px, add;
+    struct Out {};
+    __device__ __forceinline__ size_t at(int b, int o, int y, int x, int O, int, int) const
+    {
+        return (((size_t)b * O + o) * L + 2 * y + py) * W + 2 * x + px;
+    }
+    __device__ __forceinline__ Out output(int) const { return {}; }
+    __device__ __forceinline__ float operator()(Out, float v, const float *dst) const { return add ? *dst + v : v; }
 };
 
 struct EpiAffine { // act(v scale[o] + shift[o]); scale / shift: nullptr = 1 / 0
     const float *__restrict__ scale, *__restrict__ shift;
     int relu;
+    __device__ __forceinline__ size_t at(int b, int o, int y, int x, int O, int Lo, int Wo) const { return contiguous_at(b, o, y, x, O, Lo, Wo); }
     struct Out {
         float sc, sh;
     };
     __device__ __forceinline__ Out output(int o) const { return {scale ? scale[o] : 1.0f, shift ? shift[o] : 0.0f}; }
-    __device__ __forceinline__ float operator()(Out p, float v) const
+    __device__ __forceinline__ float operator()(Out p, float v, const float *) const
     {
         float val = fmaf(v, p.sc, p.sh);
         if (relu) val = val < 0.0f ? 0.0f : val; // (a NaN stays a NaN)
@@ -315,8 +340,10 @@ __global__ __launch_bounds__(kThreads) void dense_kernel(const Map m, const floa
     const bool chan_fast = m.s_chan == 1, pro = PRO && pa != nullptr;
     const int ea = vfa_dev::split_exponent(absmax[b], kExp), ew = vfa_dev::split_exponent(*(const unsigned *)packed, kExp);
     const float sa = vfa_dev::pow2f(ea);
-    const int n_chunks = m.C / kChunkC, n_iter = n_chunks * TAPS, n_first = first_chunks(m.C);
-    const u32x4 *slices = (const u32x4 *)(packed + kPackHeaderBytes) + (size_t)ot * n_iter * (kSliceHalves / 8);
+    // NT taps; a block's slices are NT of the nine of a (chunk) of the stride-2 input gradient's pack, from its class's first
+    constexpr int NT = tap_count(TAPS), PT = is_block(TAPS) ? kTaps : NT, T0 = is_block(TAPS) ? vfa_conv_grad::down_class_first(TAPS) : 0;
+    const int n_chunks = m.C / kChunkC, n_iter = n_chunks * NT, n_first = first_chunks(m.C);
+    const u32x4 *slices = (const u32x4 *)(packed + kPackHeaderBytes) + ((size_t)ot * n_chunks * PT + T0) * (kSliceHalves / 8);
     const float *ab_src = pro ? (tid < kChunkC ? pa : pb) + (size_t)b * m.C + (tid & (kChunkC - 1)) : nullptr; // threads 0 .. 63
 
     float v[WN::kLoads][4];
@@ -359,9 +386,10 @@ __global__ __launch_bounds__(kThreads) void dense_kernel(const Map m, const floa
             if (pro && tid < 2 * kChunkC) ab[tid] = ab_src[(ch + 1) * kChunkC];
         }
 #pragma unroll
-        for (int t = 0; t < TAPS; ++t) {
-            const int it = ch * TAPS + t;
-            const int next = it + 1 < n_iter ? it + 1 : it; // (the last iteration reloads its own slice into the idle buffer)
+        for (int t = 0; t < NT; ++t) {
+            const int it = ch * NT + t;
+            int next = it + 1 < n_iter ? it + 1 : it; // (the last iteration reloads its own slice into the idle buffer)
+            if constexpr (PT != NT) next = (next / NT) * PT + next % NT;
 #pragma unroll
             for (int q = 0; q < 4; ++q) w[q] = slices[(size_t)next * (kSliceHalves / 8) + tid + kThreads * q];
             const _Float16 *bw = b_lds + (it & 1) * kSliceHalves;
@@ -414,21 +442,23 @@ __global__ __launch_bounds__(kThreads) void dense_kernel(const Map m, const floa
                 const int y = y0 + 2 * wm + mi;
                 if (y >= Lo || x >= Wo) continue;
                 const float sum = TWO ? first[TWO ? n : 0][TWO ? mi : 0][i] + acc[n][mi][i] : acc[n][mi][i];
-                out[(((size_t)b * O + o) * Lo + y) * Wo + x] = epi(per_output, sum * inv);
+                float *dst = out + epi.at(b, o, y, x, O, Lo, Wo);
+                *dst = epi(per_output, sum * inv, dst);
             }
         }
 }
 
-// the grid of output tiles; the kernel's dynamic LDS is allowed once per device (vfa_conv.h: DynamicLds)
+// the grid of output tiles ((Lo_, Wo_): the cells to compute where they are not the convolution's own -- a class of EpiDown); the
+// kernel's dynamic LDS is allowed once per device (vfa_conv.h: DynamicLds)
 template <int TAPS, int S, int D, bool TWO, bool PRO, class Epi>
 int launch_dense(const Map &m, const float *a, const float *b, const unsigned *absmax, const unsigned char *packed, const Epi &epi, int O, float *out,
-                 hipStream_t s)
+                 hipStream_t s, int Lo_ = -1, int Wo_ = -1)
 {
     static DynamicLds lds;
     constexpr int lds_bytes = Win<TAPS, S, D, PRO>::kLdsBytes;
     const int status = lds.allow((const void *)dense_kernel<TAPS, S, D, TWO, PRO, Epi>, lds_bytes);
     if (status != 0) return status;
-    const int Lo = out_size(m.L, S), Wo = out_size(m.W, S);
+    const int Lo = Lo_ < 0 ? out_size(m.L, S) : Lo_, Wo = Lo_ < 0 ? out_size(m.W, S) : Wo_;
     const dim3 grid((unsigned)(tiles_x(Wo) * tiles_y(Lo)), (unsigned)out_tiles(O), (unsigned)m.B);
     hipLaunchKernelGGL((dense_kernel<TAPS, S, D, TWO, PRO, Epi>), grid, dim3(kThreads), lds_bytes, s, m, a, b, absmax, packed, epi, O, Lo, Wo, out);
     return (int)hipGetLastError();

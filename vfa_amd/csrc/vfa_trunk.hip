@@ -9,6 +9,10 @@
 //      channels, and the raw convolution acc 2^-(ea + ew) as the output.  The absmax pre-pass sees what the products see: the values
 //      AFTER the prologue, and with one tap the strided positions only.
 //   2. residual_join_kernel: out = max(fmaf(a, y, b) + (r | fmaf(ra, r, rb)), 0), one rounding per written operation.
+//   3. vfa_trunk_down_dgrad_f32, the input gradient of a stride-2 convolution (training the projection blocks): the four parity
+//      classes of dx are dense_kernel<11 | 21 | 12 | 22, 1, 1, TWO, false, EpiDown> on the output gradient -- a block of 1, 2, 2 or 4
+//      taps each, the classes' nine taps packed once per call from the weight as it lies (pack_kernel, transposed 2), the result
+//      stored through doubled strides; a 1 x 1 weight's term is dense_kernel<1, ...> added to what class (0, 0) holds.
 #include "vfa_dense.h"
 
 namespace {
@@ -37,6 +41,19 @@ int launch_trunk(const Map &m, const float *a, const float *b, const unsigned *a
 {
     return m.C > kSplitC ? launch_dense<TAPS, S, 1, true, true>(m, a, b, absmax, packed, EpiRaw{}, O, out, s)
                          : launch_dense<TAPS, S, 1, false, true>(m, a, b, absmax, packed, EpiRaw{}, O, out, s);
+}
+
+// one parity class (py, px) of the stride-2 input gradient, or (TAPS 1) the term of a 1 x 1 weight in class (0, 0): the dense kernel on
+// g (m) with the class's block of taps, stored through EpiDown; a class without positions is not launched
+template <int TAPS>
+int launch_down_class(const Map &m, const unsigned *absmax, const unsigned char *packed, int C, int L, int W, int py, int px, int add, float *dx,
+                      hipStream_t s)
+{
+    const int Lc = vfa_conv_grad::down_class_size(L, py), Wc = vfa_conv_grad::down_class_size(W, px);
+    if (Lc == 0 || Wc == 0) return 0;
+    const EpiDown epi = {L, W, py, px, add};
+    return m.C > kSplitC ? launch_dense<TAPS, 1, 1, true, false>(m, nullptr, nullptr, absmax, packed, epi, C, dx, s, Lc, Wc)
+                         : launch_dense<TAPS, 1, 1, false, false>(m, nullptr, nullptr, absmax, packed, epi, C, dx, s, Lc, Wc);
 }
 
 } // namespace
@@ -72,6 +89,43 @@ int vfa_trunk_conv_f32(const float *x, const long long *x_stride, const void *pa
     const unsigned char *pk = (const unsigned char *)packed;
     if (taps == 9) return stride == 1 ? launch_trunk<9, 1>(m, a, b, absmax, pk, O, out, s) : launch_trunk<9, 2>(m, a, b, absmax, pk, O, out, s);
     return stride == 1 ? launch_trunk<1, 1>(m, a, b, absmax, pk, O, out, s) : launch_trunk<1, 2>(m, a, b, absmax, pk, O, out, s);
+}
+
+size_t vfa_trunk_down_dgrad_workspace_bytes(int B, int O, int C, int kernel)
+{
+    if (B <= 0 || (kernel != 3 && kernel != 1) || C < 1 || C % 32 != 0) return 0;
+    const size_t packed = packed_bytes_of(C, O, kernel * kernel); // the planes of a convolution with O inputs and C outputs
+    return packed == 0 ? 0 : scales_workspace_bytes(B) + packed;
+}
+
+int vfa_trunk_down_dgrad_f32(const float *g, const long long *g_stride, const float *weight, int B, int O, int Lo, int Wo, int C, int L, int W,
+                             int kernel, int accumulate, float *dx, void *workspace, size_t workspace_bytes, void *stream)
+{
+    Map m = {};
+    if (C < 1 || O < 1 || L < 0 || W < 0 || (kernel != 3 && kernel != 1) || (accumulate != 0 && accumulate != 1)) return VFA_ERR_BAD_ARGUMENT;
+    if (Lo != out_size(L, 2) || Wo != out_size(W, 2)) return VFA_ERR_BAD_ARGUMENT; // g is not the gradient of a stride-2 map of x's size
+    int status = check_map(g, g_stride, B, O, Lo, Wo, m);
+    if (status != 0) return status == 1 ? 0 : status;
+    if (!weight || !dx || !workspace || ((uintptr_t)workspace & 15) != 0) return VFA_ERR_BAD_ARGUMENT;
+    if (C % 32 != 0 || (kernel == 1 && !accumulate)) return VFA_ERR_UNSUPPORTED;
+    const int taps = kernel * kernel;
+    const size_t packed_bytes = packed_bytes_of(C, O, taps), scales = scales_workspace_bytes(B);
+    if (packed_bytes == 0 || out_tiles(C) > 65535) return VFA_ERR_UNSUPPORTED;
+    if (workspace_bytes < scales + packed_bytes) return VFA_ERR_BAD_ARGUMENT;
+    hipStream_t s = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(workspace, 0, scales, s);
+    if (e != hipSuccess) return (int)e;
+    launch_absmax(m, nullptr, nullptr, Lo, Wo, 1, (unsigned *)workspace, s); // the whole of g: one scale per image for every class
+    unsigned char *packed = (unsigned char *)workspace + scales;
+    status = pack_weights(weight, C, O, taps, kernel == 3 ? 2 : 1, packed, packed_bytes, stream);
+    if (status != 0) return status;
+    const unsigned *absmax = (const unsigned *)workspace;
+    if (kernel == 1) return launch_down_class<1>(m, absmax, packed, C, L, W, 0, 0, 1, dx, s);
+    status = launch_down_class<11>(m, absmax, packed, C, L, W, 0, 0, accumulate, dx, s);
+    if (status == 0) status = launch_down_class<21>(m, absmax, packed, C, L, W, 1, 0, accumulate, dx, s);
+    if (status == 0) status = launch_down_class<12>(m, absmax, packed, C, L, W, 0, 1, accumulate, dx, s);
+    if (status == 0) status = launch_down_class<22>(m, absmax, packed, C, L, W, 1, 1, accumulate, dx, s);
+    return status;
 }
 
 int vfa_residual_join_f32(const float *y, const float *a, const float *b, const float *r, const float *ra, const float *rb, int B, int C, int L,

@@ -1954,6 +1954,159 @@ def residual_block_train(x, w1, g1, b1, w2, g2, b2, groups=16, eps=1e-5):
     return _ResidualBlockTrain.apply(x, w1, g1, b1, w2, g2, b2, int(groups), float(eps))
 
 
+def _down_size(n):
+    return (n - 1) // 2 + 1 if n else 0
+
+
+def trunk_down_weight_grad(grad, x, kernel):
+    """dL/dweight of a stride-2 convolution of the trunk (``vfa_trunk_down_wgrad_f32``): ``kernel`` 3 for ``y = F.conv2d(x, weight,
+    stride=2, padding=1)`` -> (O, C, 3, 3), 1 for ``y = F.conv2d(x, weight, stride=2)`` -> (O, C, 1, 1); grad = dL/dy (B, O, Lo, Wo)
+    with ``Lo = (L - 1) // 2 + 1``, x (B, C, L, W), both float32 and read through their strides, O and C multiples of 32.  The
+    kernels of ``trunk_conv_weight_grad`` on K tiles of 2 x 32 cells, ``slabs_for(Lo, Wo, O, C)`` slabs merged in float64 in ascending
+    order: the same bits on every run."""
+    if int(kernel) not in (3, 1):
+        raise ValueError(f"trunk_down_weight_grad: kernel must be 3 or 1, got {kernel}")
+    if x.dtype != torch.float32 or x.dim() != 4 or grad.dtype != torch.float32 or grad.dim() != 4 or grad.shape[0] != x.shape[0] \
+            or tuple(grad.shape[2:]) != (_down_size(x.shape[2]), _down_size(x.shape[3])):
+        raise ValueError(f"trunk_down_weight_grad: grad (B, O, Lo, Wo) and x (B, C, L, W) must be float32 maps with (Lo, Wo) the stride-2 "
+                         f"size of (L, W), got {grad.dtype} {tuple(grad.shape)} and {x.dtype} {tuple(x.shape)}")
+    B, C, L, W = x.shape
+    O = int(grad.shape[1])
+    if C % 32 or O % 32 or not C or not O:
+        raise ValueError(f"trunk_down_weight_grad: C and O must be multiples of 32, got {C} and {O}")
+    _lib.require_device(grad, x)
+    grad, x, k = grad.detach(), x.detach(), int(kernel)
+    dw = torch.empty((O, C, k, k), dtype=torch.float32, device=x.device)
+    ws_bytes = _lib.lib().vfa_trunk_down_wgrad_workspace_bytes(B, O, C, L, W, k)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+    _launch("vfa_trunk_down_wgrad_f32", _lib.ptr(grad), (ctypes.c_longlong * 4)(*grad.stride()), _lib.ptr(x), (ctypes.c_longlong * 4)(*x.stride()),
+            B, C, L, W, O, k, _lib.ptr(dw), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(), tag=(B, C, L, W, O, k))
+    return dw
+
+
+def trunk_down_input_grad(grad, weight, size, add_to=None):
+    """dL/dx of a stride-2 convolution of the trunk (``vfa_trunk_down_dgrad_f32``) from grad = dL/dy (B, O, Lo, Wo), read through its
+    strides, and ``weight`` (O, C, 3, 3) (padding 1) or (O, C, 1, 1) as it lies; ``size = (L, W)`` of x, which stride 2 does not
+    determine: ``(L - 1) // 2 + 1`` must be Lo -> (B, C, L, W) contiguous.  The four parity classes of dx are four launches of the
+    dense kernel over their own 1, 2, 2 and 4 taps; every element is written exactly once; an image gives the same bits alone and in a
+    batch.  ``add_to``: a contiguous (B, C, L, W) map to which the gradient is added in place, ``add_to + gradient`` in that order
+    (returned) -- the only form a 1 x 1 weight has, whose gradient touches the even positions alone."""
+    if weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[2:]) not in ((3, 3), (1, 1)) or weight.shape[0] % 32 \
+            or weight.shape[1] % 32:
+        raise ValueError(f"trunk_down_input_grad: weight must be float32 (O, C, 3, 3) or (O, C, 1, 1) with O and C multiples of 32, got "
+                         f"{weight.dtype} {tuple(weight.shape)}")
+    O, C, k = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
+    L, W = (int(v) for v in size)
+    if grad.dtype != torch.float32 or grad.dim() != 4 or tuple(grad.shape[1:]) != (O, _down_size(L), _down_size(W)) or L < 1 or W < 1:
+        raise ValueError(f"trunk_down_input_grad: grad must be float32 (B, {O}, {_down_size(L)}, {_down_size(W)}) for size {(L, W)}, got "
+                         f"{grad.dtype} {tuple(grad.shape)}")
+    B = int(grad.shape[0])
+    if add_to is None and k == 1:
+        raise ValueError("trunk_down_input_grad: the gradient of a 1 x 1 weight is added to a map (add_to)")
+    if add_to is not None and (add_to.dtype != torch.float32 or tuple(add_to.shape) != (B, C, L, W) or not add_to.is_contiguous()):
+        raise ValueError(f"trunk_down_input_grad: add_to must be a contiguous float32 {(B, C, L, W)} map, got {add_to.dtype} {tuple(add_to.shape)}")
+    _lib.require_device(grad, weight, add_to)
+    grad, w = grad.detach(), weight.detach().contiguous()
+    dx = torch.empty((B, C, L, W), dtype=torch.float32, device=grad.device) if add_to is None else add_to
+    if dx.numel() == 0:
+        return dx
+    ws_bytes = _lib.lib().vfa_trunk_down_dgrad_workspace_bytes(B, O, C, k)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=grad.device)
+    _launch("vfa_trunk_down_dgrad_f32", _lib.ptr(grad), (ctypes.c_longlong * 4)(*grad.stride()), _lib.ptr(w), B, O, int(grad.shape[2]),
+            int(grad.shape[3]), C, L, W, k, int(add_to is not None), _lib.ptr(dx), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(),
+            tag=(B, O, C, L, W, k, add_to is not None))
+    return dx
+
+
+class _ProjectionBlockTrain(torch.autograd.Function):
+    """``projection_block_train``: one node for the whole projection block, like ``_ResidualBlockTrain``.  Four maps are kept
+    besides the input (y1, y2, yd and the join); the packed planes are made per call and kept nowhere."""
+
+    @staticmethod
+    def forward(ctx, x, w1, g1, b1, w2, g2, b2, wd, gd, bd, groups, eps):
+        B, C, L, W = x.shape
+        O = int(w1.shape[0])
+        x = x.detach().contiguous()
+        Lo, Wo = _down_size(L), _down_size(W)
+
+        def conv(t, w, sizes, stride, a=None, b=None):
+            taps = int(w.shape[2]) * int(w.shape[3])
+            nbytes = _lib.lib().vfa_trunk_packed_bytes(int(w.shape[0]), int(w.shape[1]), taps)
+            packed = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+            _launch("vfa_trunk_pack_weights_f32", _lib.ptr(w.detach().contiguous()), int(w.shape[0]), int(w.shape[1]), taps, _lib.ptr(packed), nbytes,
+                    _lib.current_stream_handle(), tag=(int(w.shape[0]), int(w.shape[1]), taps))
+            return _trunk_conv_launch(t, (ctypes.c_longlong * 4)(*t.stride()), packed, nbytes, a, b, sizes, taps, stride)
+        y1 = conv(x, w1, (B, C, L, W, O), 2)
+        a1, c1, s1 = group_norm_stats(y1, groups, g1, b1, eps)
+        y2 = conv(y1, w2, (B, O, Lo, Wo, O), 1, a1, c1)
+        a2, c2, s2 = group_norm_stats(y2, groups, g2, b2, eps)
+        yd = conv(x, wd, (B, C, L, W, O), 2)
+        ad, cd, sd = group_norm_stats(yd, groups, gd, bd, eps)
+        out = residual_join(y2, (a2, c2), yd, (ad, cd))
+        ctx.save_for_backward(x, y1, y2, yd, out, a1, c1, s1, a2, c2, s2, ad, cd, sd, w1, g1, w2, g2, wd, gd)
+        ctx.groups = groups
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        x, y1, y2, yd, out, a1, c1, s1, a2, c2, s2, ad, cd, sd, w1, g1, w2, g2, wd, gd = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx = dw1 = dg1 = db1 = dw2 = dwd = None
+        dy2, dz, dg2, db2 = group_norm_backward(grad, y2, a2, c2, g2, s2, ctx.groups, mask_out=out, want_params=need[5] or need[6])
+        dyd = dgd = dbd = None
+        if need[0] or any(need[7:10]):
+            # the projection's GroupNorm sits behind the same ReLU: u = dz, and m ? dz : 0 is dz bit for bit (the second dz is dropped)
+            dyd, _, dgd, dbd = group_norm_backward(dz, yd, ad, cd, gd, sd, ctx.groups, mask_out=out, want_params=need[8] or need[9])
+        del dz
+        if need[4]:
+            dw2 = trunk_conv_weight_grad(dy2, y1, (a1, c1))
+        if need[7]:
+            dwd = trunk_down_weight_grad(dyd, x, 1)
+        if any(need[:4]):
+            dx1 = trunk_conv_input_grad(dy2, w2)
+            del dy2
+            dy1, dg1, db1 = group_norm_backward(dx1, y1, a1, c1, g1, s1, ctx.groups, want_params=need[2] or need[3])
+            del dx1
+            if need[1]:
+                dw1 = trunk_down_weight_grad(dy1, x, 3)
+            if need[0]:
+                dx = trunk_down_input_grad(dy1, w1, x.shape[2:])               # the 3 x 3 term first,
+                dx = trunk_down_input_grad(dyd, wd, x.shape[2:], add_to=dx)   # then the projection's, added to it
+        return (dx, dw1, dg1 if need[2] else None, db1 if need[3] else None, dw2, dg2 if need[5] else None, db2 if need[6] else None,
+                dwd, dgd if need[8] else None, dbd if need[9] else None, None, None)
+
+
+def projection_block_train(x, w1, g1, b1, w2, g2, b2, wd, gd, bd, groups=16, eps=1e-5):
+    """A projection block of the trunk with gradients, on the HIP kernels: ``relu(gn2(conv2(relu(gn1(conv1(x))))) + gnd(convd(x)))``
+    with ``conv1`` 3 x 3 of stride 2 (w1: (O, C, 3, 3)), ``conv2`` 3 x 3 of stride 1 (w2: (O, O, 3, 3)), ``convd`` 1 x 1 of stride 2
+    (wd: (O, C, 1, 1)), all without bias, C and O multiples of 32, and GroupNorms of ``groups`` groups (g, b: (O)); x (B, C, L, W)
+    float32 -> (B, O, Lo, Wo) contiguous with ``Lo = (L - 1) // 2 + 1``, the bits of ``_Block.forward_hip`` under ``no_grad``.  ONE
+    once-differentiable node.  Forward: the calls of ``forward_hip`` with ``group_norm_stats`` and a join that is not in place; x, the
+    three raw maps, the join, the affines and the statistics are saved -- four maps besides the input.  Backward:
+    ``group_norm_backward`` with the join's mask (-> dy2 and dz), the same entry point once more on (dz, yd) for the projection's
+    GroupNorm, ``trunk_conv_weight_grad`` / ``trunk_conv_input_grad`` / ``group_norm_backward`` for conv2 and the first GroupNorm as in
+    ``residual_block_train``, ``trunk_down_weight_grad`` for w1 and wd, and dx = ``trunk_down_input_grad`` of (dy1, w1), then that of
+    (dyd, wd) added to it -- only what ``needs_input_grad`` asks for.  Fixed summation order, no float atomics: the same bits on every
+    run without ``torch.use_deterministic_algorithms``, and an image's dx alone and in a batch; no host wait, capturable."""
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] % 32 or x.numel() == 0:
+        raise ValueError(f"projection_block_train: x must be a float32 (B, C, L, W) map with values and C a multiple of 32, got {x.dtype} {tuple(x.shape)}")
+    C = int(x.shape[1])
+    O = int(w1.shape[0]) if w1.dim() == 4 else 0
+    if O < 1 or O % 32:
+        raise ValueError(f"projection_block_train: O must be a multiple of 32, got w1 {tuple(w1.shape)}")
+    if int(groups) < 1 or O % int(groups):
+        raise ValueError(f"projection_block_train: groups must divide O = {O}, got {groups}")
+    for w, shape in ((w1, (O, C, 3, 3)), (w2, (O, O, 3, 3)), (wd, (O, C, 1, 1))):
+        if w.dtype != torch.float32 or tuple(w.shape) != shape:
+            raise ValueError(f"projection_block_train: a weight must be float32 {shape}, got {w.dtype} {tuple(w.shape)}")
+    for t in (g1, b1, g2, b2, gd, bd):
+        if t.dtype != torch.float32 or tuple(t.shape) != (O,):
+            raise ValueError(f"projection_block_train: a GroupNorm parameter must be float32 ({O},), got {t.dtype} {tuple(t.shape)}")
+    _lib.require_device(x, w1, g1, b1, w2, g2, b2, wd, gd, bd)
+    return _ProjectionBlockTrain.apply(x, w1, g1, b1, w2, g2, b2, wd, gd, bd, int(groups), float(eps))
+
+
 _STEM_MAX_OUT = 64      # kMaxOut of csrc/vfa_stem.h
 
 

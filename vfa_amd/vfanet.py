@@ -30,6 +30,11 @@ GroupNorm, ReLU and the max pooling -- at inference on the HIP kernels of ``csrc
 residual blocks -- stride 1, no projection: 5 of resnet18's 8, 13 of resnet34's 16 -- WITH gradients on ``ops.residual_block_train``,
 one autograd node per block that keeps three maps instead of the library's five (``csrc/vfa_trunk_grad.hip``; ``trunk``; DESIGN.md
 4.6).  The projection blocks and the stem stay the modules they are.
+
+``trunk_proj_train="hip"`` (independent of the three; default ``"library"``) runs the trunk's three projection blocks -- stride 2 and
+a 1 x 1 projection: the first block of ``layer2`` .. ``layer4`` -- WITH gradients on ``ops.projection_block_train``, one node per block
+that keeps four maps; the gradients of the stride-2 convolutions are ``vfa_trunk_down_wgrad_f32`` and ``vfa_trunk_down_dgrad_f32``
+(DESIGN.md 4.6).  With both training switches on ``"hip"`` only the stem runs as a module.
 """
 import glob
 import os
@@ -64,6 +69,8 @@ TRUNK_CONVS = ("library", "hip")
 TRUNK_STEM = ("library", "hip")
 # Who runs the trunk's identity residual blocks where gradients are enabled (``VFANet.trunk_convs_train``, ``VFANet.trunk``)
 TRUNK_CONVS_TRAIN = ("library", "hip")
+# Who runs the trunk's projection blocks where gradients are enabled (``VFANet.trunk_proj_train``, ``VFANet.trunk``)
+TRUNK_PROJ_TRAIN = ("library", "hip")
 
 
 def _find_pretrained(base):
@@ -144,12 +151,21 @@ class _Block(nn.Module):
         """Stride 1 and no projection: the shortcut is x itself."""
         return self.downsample is None and self.conv1.stride[0] == 1
 
+    @property
+    def is_projection(self):
+        """Stride 2 and a 1 x 1 projection with its GroupNorm as the shortcut."""
+        return self.downsample is not None and self.conv1.stride[0] == 2
+
     def forward_train_hip(self, x):
-        """``forward`` of an identity block with gradients on ``ops.residual_block_train``: the calls of ``forward_hip`` and their
-        bits, and a backward on the HIP kernels from three kept maps."""
-        assert self.is_identity
-        return ops.residual_block_train(x, self.conv1.weight, self.bn1.weight, self.bn1.bias, self.conv2.weight, self.bn2.weight,
-                                        self.bn2.bias, self.bn1.num_groups, self.bn1.eps)
+        """``forward`` with gradients: an identity block on ``ops.residual_block_train``, a projection block on
+        ``ops.projection_block_train`` -- the calls of ``forward_hip`` and their bits, and a backward on the HIP kernels from three
+        or four kept maps."""
+        first = (x, self.conv1.weight, self.bn1.weight, self.bn1.bias, self.conv2.weight, self.bn2.weight, self.bn2.bias)
+        if self.is_identity:
+            return ops.residual_block_train(*first, self.bn1.num_groups, self.bn1.eps)
+        assert self.is_projection
+        return ops.projection_block_train(*first, self.downsample[0].weight, self.downsample[1].weight, self.downsample[1].bias,
+                                          self.bn1.num_groups, self.bn1.eps)
 
 
 def _gn_affine(y, gn):
@@ -198,12 +214,14 @@ class _Trunk(nn.Module):
             maps.append(x)
         return maps[1], maps[2], maps[3]
 
-    def stages_train_hip(self, x):
-        """``stages`` with gradients: each identity block on ``_Block.forward_train_hip``, every other block the module it is."""
+    def stages_train_hip(self, x, identity=True, projection=False):
+        """``stages`` with gradients: the identity blocks (``identity``) and the projection blocks (``projection``) on
+        ``_Block.forward_train_hip``, every other block the module it is."""
         maps = []
         for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
             for block in layer:
-                x = block.forward_train_hip(x) if block.is_identity else block(x)
+                hip = (identity and block.is_identity) or (projection and block.is_projection)
+                x = block.forward_train_hip(x) if hip else block(x)
             maps.append(x)
         return maps[1], maps[2], maps[3]
 
@@ -236,6 +254,7 @@ class VFANet(nn.Module):
         self.trunk_convs = "library"  # or "hip" (``trunk``); the same kind of attribute
         self.trunk_stem = "library"  # or "hip" (``trunk``); the same kind of attribute, independent of ``trunk_convs``
         self.trunk_convs_train = "library"  # or "hip" (``trunk``, with gradients); the same kind of attribute, independent of both
+        self.trunk_proj_train = "library"  # or "hip" (``trunk``, with gradients: the projection blocks); independent of the three
         self.input_size = getattr(args, "resize_size", None)  # (H, W) uint8 frames are resized to (train.py:209-214); None: as they are
         self.base = _Trunk(_DEPTHS[base])
         if pretrained:
@@ -276,7 +295,9 @@ class VFANet(nn.Module):
         anywhere else, and with both settings on ``"library"``, this is ``self.base(x)``.
         ``trunk_convs_train`` names who runs the identity residual blocks where gradients are enabled (``"hip"``: the kernels of
         ``csrc/vfa_trunk_grad.hip``, ``_Trunk.stages_train_hip``; the stem and the projection blocks run as modules): it holds where
-        gradients are enabled and ``x`` is a float32 CUDA tensor with at least one image, in training and in eval mode alike."""
+        gradients are enabled and ``x`` is a float32 CUDA tensor with at least one image, in training and in eval mode alike.
+        ``trunk_proj_train`` names who runs the three projection blocks (the first of ``layer2`` .. ``layer4``) under the same
+        conditions (``"hip"``: ``ops.projection_block_train``); with both on ``"hip"`` only the stem runs as a module."""
         if self.trunk_convs not in TRUNK_CONVS:
             raise ValueError(f"VFANet.trunk: trunk_convs is one of {TRUNK_CONVS}, got {self.trunk_convs!r}")
         if self.trunk_stem not in TRUNK_STEM:
@@ -287,9 +308,11 @@ class VFANet(nn.Module):
                 and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0):
             y = self.base.stem_hip(x) if self.trunk_stem == "hip" else self.base.stem(x)
             return self.base.stages_hip(y) if self.trunk_convs == "hip" else self.base.stages(y)
-        if (self.trunk_convs_train == "hip" and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-                and x.numel() > 0):
-            return self.base.stages_train_hip(self.base.stem(x))
+        if self.trunk_proj_train not in TRUNK_PROJ_TRAIN:
+            raise ValueError(f"VFANet.trunk: trunk_proj_train is one of {TRUNK_PROJ_TRAIN}, got {self.trunk_proj_train!r}")
+        if ("hip" in (self.trunk_convs_train, self.trunk_proj_train) and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
+                and x.dim() == 4 and x.numel() > 0):
+            return self.base.stages_train_hip(self.base.stem(x), self.trunk_convs_train == "hip", self.trunk_proj_train == "hip")
         return self.base(x)
 
     def laterals(self, images):
