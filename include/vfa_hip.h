@@ -1095,6 +1095,39 @@ int vfa_stem_conv_f32(const float *x, const long long *x_stride, const float *we
                       void *workspace, size_t workspace_bytes, void *stream);
 int vfa_stem_pool_f32(const float *y, const float *a, const float *b, int B, int C, int L, int W, float *out, void *stream);
 
+/* ---- the stem with gradients (csrc/vfa_stem.hip; the integer rules: csrc/vfa_stem.h) -----------------------------------------------
+ * The two backward kernels the stem needs besides vfa_group_norm_backward_f32 (VFA_GN_MASK_PROLOGUE on the raw map).  float32; no
+ * atomics, fixed summation orders: the same bits on every run and on devices of any size.  Stream-ordered, no host wait, capturable.
+ *
+ * vfa_stem_pool_backward_f32: the backward of vfa_stem_pool_f32 up to, but not through, the ReLU.  gout (B, C, Lo, Wo) is the
+ *   gradient of the pooled map, y (B, C, L, W) the raw map, a, b (B, C) the forward's affine, all contiguous; u (B, C, L, W), every
+ *   element written exactly once: u[b, c, p, q] = the sum of gout[b, c, i, j] over the windows (i, j) whose winning tap is (p, q),
+ *   added in ascending (i, j) order from +0 (a position that wins nowhere: +0).  A window's taps max(fmaf(a, y, b), 0) are recomputed
+ *   with the forward's bits (no winner is saved by the forward) and scanned as the forward scans them, rows then columns ascending,
+ *   taps outside the map skipped, under the forward's rule (t > best || t != t): the first of equal maxima wins, and a NaN takes the
+ *   window, the last one in scan order -- torch's rule.  The ReLU's mask is NOT applied: a window whose maximum is 0 credits its first
+ *   tap, and vfa_group_norm_backward_f32 removes it.  A gather per element of u: an image gives the same bits alone and in a batch.
+ *   Any C >= 1.
+ * vfa_stem_conv_wgrad_f32: dw (O, 3, 7, 7) contiguous, dw[o, c, ky, kx] = sum over b, then (i, j), of
+ *   g[b, o, i, j] x[b, c, 2 i + ky - 3, 2 j + kx - 3], positions outside the image being zeros; g (B, O, Lo, Wo) contiguous, x
+ *   (B, 3, L, W) read through its four element strides x_stride[4] (>= 0, never copied), 1 <= O <= 64.  No bias, no input gradient.
+ *   The exact f32 MFMA with the output cells as K: the cells are cut into vfa_stem::wgrad_slabs(Lo, Wo) <= 64 slabs of consecutive
+ *   4 x 32 tiles, a rule of (Lo, Wo) alone; an (image, slab) is one workgroup whose four waves each sum one row of every tile in
+ *   ascending cell order, merged as ((w0 + w1) + w2) + w3 into one float32 partial; the partials of an element are added in float64,
+ *   images then slabs ascending, and rounded once.  Integer-valued operands whose partial sums stay below 2^24 give float64's result
+ *   exactly.  workspace: vfa_stem_conv_wgrad_workspace_bytes(B, O, L, W) = B * slabs * O * 147 * 4 bytes, 16-byte aligned (0 for an
+ *   empty or unsupported problem).
+ *
+ * Errors, decided before anything is launched: a negative size, O < 1, a NULL required pointer (dw always), a negative element
+ * stride, a short or misaligned workspace: VFA_ERR_BAD_ARGUMENT; O > 64, B or L > 65535, L * W >= 2^30, an image whose offsets pass
+ * 2^31 (the pooling: B * C >= 2^31): VFA_ERR_UNSUPPORTED.  An empty problem (B == 0 or L * W == 0; the pooling: C == 0 too) returns 0:
+ * dw is zeros, u is not written. */
+int vfa_stem_pool_backward_f32(const float *gout, const float *y, const float *a, const float *b, int B, int C, int L, int W, float *u,
+                               void *stream);
+size_t vfa_stem_conv_wgrad_workspace_bytes(int B, int O, int L, int W);
+int vfa_stem_conv_wgrad_f32(const float *g, const float *x, const long long *x_stride, int B, int L, int W, int O, float *dw, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,9 @@ SIGNATURES = {
     "vfa_stem_workspace_bytes": [_c_int],
     "vfa_stem_conv_f32": [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_size_t, _vp],
     "vfa_stem_pool_f32": [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp],
+    "vfa_stem_pool_backward_f32": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp],
+    "vfa_stem_conv_wgrad_workspace_bytes": [_c_int, _c_int, _c_int, _c_int],
+    "vfa_stem_conv_wgrad_f32": [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_size_t, _vp],
     "vfa_group_norm_stats_f32": [_vp, _vp, _vp, _vp, _c_float, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_size_t, _vp],
     "vfa_group_norm_backward_workspace_bytes": [_c_int, _c_int],
     "vfa_group_norm_backward_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp,

@@ -1,6 +1,6 @@
 // vfa_stem.h -- the integer rules of the trunk's stem of vfa_stem.hip (host / device code; tests/native/stem_harness.cpp checks them
 // against a brute-force enumeration): the 7 x 7 stride-2 convolution of three channels with zero padding 3, and the 3 x 3 stride-2
-// max pooling with padding 1 behind it.
+// max pooling with padding 1 behind it; at the end, the rules of the two backward kernels.
 //
 // Convolution.  The output is (Lo, Wo) = (conv_out(L), conv_out(W)).  A tile is kTileRows x kTileCols OUTPUT cells and all (at most
 // kMaxOut) outputs; the cell (ry, rx) of the tile at (y0, x0) is output position (y0 + ry, x0 + rx).  Its window is the
@@ -104,6 +104,43 @@ VFA_STEM_HD constexpr int packed_index(int o, int k) { return k * kMaxOut + 2 * 
 // the pooling's taps of output o along an axis of n positions
 VFA_STEM_HD int pool_first(int o) { return 2 * o - 1 < 0 ? 0 : 2 * o - 1; }
 VFA_STEM_HD int pool_last(int o, int n) { return 2 * o + 1 > n - 1 ? n - 1 : 2 * o + 1; }
+
+// ---- the backward rules (vfa_stem_pool_backward_f32, vfa_stem_conv_wgrad_f32; tests/native/stem_grad_harness.cpp checks them) ----------
+//
+// Pooling.  Along an axis position p lies in the windows pool_window_first(p) .. pool_window_last(p, n_out) of the n_out outputs:
+// an even position in one, an odd one in two unless the second is past the last output.  A window's taps are scanned rows
+// ascending, columns ascending inside a row, the taps outside the map skipped: pool_scan_rank is a tap's place in that order
+// (0 .. pool_taps(oy, L) pool_taps(ox, W) - 1).  The WINNER of a window is kept as a code that does not depend on the map's size:
+// pool_tap_code = 3 (ty - (2 oy - 1)) + (tx - (2 ox - 1)), 0 .. 8, kNoWinner for a window past the map.
+VFA_STEM_HD int pool_window_first(int p) { return p / 2; }
+VFA_STEM_HD int pool_window_last(int p, int n_out) { return (p + 1) / 2 > n_out - 1 ? n_out - 1 : (p + 1) / 2; }
+VFA_STEM_HD int pool_taps(int o, int n) { return pool_last(o, n) - pool_first(o) + 1; }
+VFA_STEM_HD int pool_scan_rank(int oy, int ox, int ty, int tx, int W) { return (ty - pool_first(oy)) * pool_taps(ox, W) + (tx - pool_first(ox)); }
+VFA_STEM_HD int pool_tap_code(int oy, int ox, int ty, int tx) { return 3 * (ty - (2 * oy - 1)) + (tx - (2 * ox - 1)); }
+constexpr int kNoWinner = 255;
+
+// A workgroup of the pooling's backward owns a tile of kPoolTileRows x kPoolTileCols positions of u at an even origin (p0, q0).  The
+// windows that contain them are kPoolWinRows x kPoolWinCols, from window (p0 / 2, q0 / 2); their taps are kPoolTapRows x kPoolTapCols
+// positions from (p0 - 1, q0 - 1).
+constexpr int kPoolTileRows = 32, kPoolTileCols = 64;
+constexpr int kPoolWinRows = kPoolTileRows / 2 + 1, kPoolWinCols = kPoolTileCols / 2 + 1;
+constexpr int kPoolTapRows = kPoolTileRows + 3, kPoolTapCols = kPoolTileCols + 3;
+VFA_STEM_HD int pool_tiles_x(int W) { return (W + kPoolTileCols - 1) / kPoolTileCols; }
+VFA_STEM_HD int pool_tiles_y(int L) { return (L + kPoolTileRows - 1) / kPoolTileRows; }
+
+// Weight gradient.  The output cells are the K dimension of the product.  They are walked in the forward's tiles (tile_origin),
+// row-major over the (Lo, Wo) map, and a SLAB is a run of consecutive tiles.  The cut is a function of (Lo, Wo) alone: a map of n
+// tiles has min(n, kMaxSlabs) slabs and slab s owns the tiles [n s / slabs, n (s + 1) / slabs) -- never empty, every tile in exactly
+// one slab -- so what is summed where depends on neither the device nor the batch (the rule of vfa_conv_grad.h).  One (image, slab)
+// gives one float32 partial of O x kK floats, [image][slab][o][k].
+constexpr int kMaxSlabs = 64;
+constexpr int kNBlocks = (kK + 31) / 32;  // 32-column MFMA blocks of the taps: N = 147 padded to 160
+VFA_STEM_HD int wgrad_tiles(int Lo, int Wo) { return tiles_x(Wo) * tiles_y(Lo); }
+VFA_STEM_HD int wgrad_slabs(int Lo, int Wo) { return wgrad_tiles(Lo, Wo) < kMaxSlabs ? wgrad_tiles(Lo, Wo) : kMaxSlabs; }
+// first tile of slab s (s == slabs: one past the last tile)
+VFA_STEM_HD int wgrad_slab_begin(int s, int Lo, int Wo) { return (int)((long long)wgrad_tiles(Lo, Wo) * s / wgrad_slabs(Lo, Wo)); }
+VFA_STEM_HD size_t wgrad_partial_floats(int O) { return (size_t)O * kK; }
+VFA_STEM_HD size_t wgrad_partial_index(int b, int s, int n_slabs, int o, int k, int O) { return ((size_t)b * n_slabs + s) * wgrad_partial_floats(O) + (size_t)o * kK + k; }
 
 } // namespace vfa_stem
 #endif // VFA_STEM_H

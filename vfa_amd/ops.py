@@ -2153,3 +2153,107 @@ def stem_pool(y, affine):
         _launch("vfa_stem_pool_f32", _lib.ptr(y), _lib.ptr(a), _lib.ptr(b), B, C, L, W, _lib.ptr(out), _lib.current_stream_handle(),
                 tag=(B, C, L, W))
     return out
+
+
+def stem_pool_backward(gout, y, affine):
+    """The backward of ``stem_pool`` up to, but not through, the ReLU (``vfa_stem_pool_backward_f32``): gout (B, C, Lo, Wo), the
+    gradient of the pooled map, y (B, C, L, W) the raw map and ``affine = (a, b)`` the forward's -> u (B, C, L, W) contiguous,
+    ``u[b, c, p, q]`` the sum of gout over the windows whose winning tap is (p, q), in ascending window order from +0.  The taps are
+    recomputed with the forward's bits and the winner is the forward's: the first of equal maxima, the last NaN.  The ReLU's mask
+    is not applied -- u is the gradient behind the ReLU that ``group_norm_backward`` expects.  A gather, no atomics: the same bits
+    on every run, and an image alone and in a batch."""
+    a, b = affine
+    _lib.require_device(gout, y, a, b)
+    if y.dtype != torch.float32 or y.dim() != 4:
+        raise ValueError(f"stem_pool_backward: y must be float32 (B, C, L, W), got {y.dtype} {tuple(y.shape)}")
+    B, C, L, W = y.shape
+    Lo, Wo = (_down_size(L), _down_size(W)) if L and W else (0, 0)
+    if gout.dtype != torch.float32 or tuple(gout.shape) != (B, C, Lo, Wo):
+        raise ValueError(f"stem_pool_backward: gout must be float32 {(B, C, Lo, Wo)}, got {gout.dtype} {tuple(gout.shape)}")
+    for t in (a, b):
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, C):
+            raise ValueError(f"stem_pool_backward: the affine is two float32 ({B}, {C}) tensors, got {t.dtype} {tuple(t.shape)}")
+    gout, y, a, b = gout.detach().contiguous(), y.detach().contiguous(), a.detach().contiguous(), b.detach().contiguous()
+    u = torch.empty_like(y)
+    if u.numel():
+        _launch("vfa_stem_pool_backward_f32", _lib.ptr(gout), _lib.ptr(y), _lib.ptr(a), _lib.ptr(b), B, C, L, W, _lib.ptr(u),
+                _lib.current_stream_handle(), tag=(B, C, L, W))
+    return u
+
+
+def stem_conv_weight_grad(grad, x):
+    """dL/dweight (O, 3, 7, 7) of ``y = F.conv2d(x, weight, stride=2, padding=3)`` (``stem_conv``) from grad = dL/dy
+    (B, O, (L - 1) // 2 + 1, (W - 1) // 2 + 1) and the images x (B, 3, L, W), read through their strides and never copied
+    (``vfa_stem_conv_wgrad_f32``), O <= 64.  The exact f32 MFMA with the output cells as K; slabs of ``wgrad_slabs(Lo, Wo)``
+    (``csrc/vfa_stem.h``), one float32 partial per (image, slab), merged in float64 in ascending order and rounded once: the same
+    bits on every run; integer-valued operands give float64's result exactly.  No host wait, capturable."""
+    _lib.require_device(grad, x)
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"stem_conv_weight_grad: x must be float32 (B, 3, L, W), got {x.dtype} {tuple(x.shape)}")
+    B, _, L, W = x.shape
+    Lo, Wo = (_down_size(L), _down_size(W)) if L and W else (0, 0)
+    if grad.dtype != torch.float32 or grad.dim() != 4 or grad.shape[0] != B or tuple(grad.shape[2:]) != (Lo, Wo) \
+            or not 1 <= grad.shape[1] <= _STEM_MAX_OUT:
+        raise ValueError(f"stem_conv_weight_grad: grad must be float32 ({B}, O <= {_STEM_MAX_OUT}, {Lo}, {Wo}), got {grad.dtype} {tuple(grad.shape)}")
+    O = int(grad.shape[1])
+    grad, x = grad.detach().contiguous(), x.detach()
+    dw = torch.empty((O, 3, 7, 7), dtype=torch.float32, device=x.device)
+    ws_bytes = _lib.lib().vfa_stem_conv_wgrad_workspace_bytes(B, O, L, W)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+    _launch("vfa_stem_conv_wgrad_f32", _lib.ptr(grad), _lib.ptr(x), (ctypes.c_longlong * 4)(*x.stride()), B, L, W, O, _lib.ptr(dw), _lib.ptr(ws),
+            ws_bytes, _lib.current_stream_handle(), tag=(B, L, W, O))
+    return dw
+
+
+class _StemTrain(torch.autograd.Function):
+    """``stem_train``: one node for the whole stem.  Besides the images only the raw map is kept; the normalised map is never
+    written and the pooling keeps no index map -- its winners are recomputed from the raw map in the backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, groups, eps):
+        x = x.detach()
+        y = stem_conv(x, weight)
+        a, b, stats = group_norm_stats(y, groups, gamma, beta, eps)
+        out = stem_pool(y, (a, b))
+        ctx.save_for_backward(x, y, a, b, stats, gamma, weight)
+        ctx.groups = groups
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        x, y, a, b, stats, gamma, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dw = dgamma = dbeta = None
+        if any(need[1:4]):
+            u = stem_pool_backward(grad, y, (a, b))
+            dy, dgamma, dbeta = group_norm_backward(u, y, a, b, gamma, stats, ctx.groups, want_params=need[2] or need[3])
+            del u
+            if need[1]:
+                dw = stem_conv_weight_grad(dy, x)
+        return None, dw, dgamma if need[2] else None, dbeta if need[3] else None, None, None
+
+
+def stem_train(x, weight, gamma, beta, groups=16, eps=1e-5):
+    """The trunk's stem with gradients, on the HIP kernels: ``max_pool2d(relu(group_norm(conv2d(x, weight, stride=2, padding=3))), 3,
+    2, 1)`` with weight (O, 3, 7, 7), O <= 64, without bias, and a GroupNorm of ``groups`` groups (gamma, beta: (O)); x (B, 3, L, W)
+    float32, read through its strides -> the pooled map, contiguous, the bits of ``_Trunk.stem_hip`` under ``no_grad``.  ONE
+    once-differentiable node.  Forward: ``stem_conv``, ``group_norm_stats``, ``stem_pool``; x, the raw map, the affine, the
+    statistics, gamma and the weight are saved -- one map besides the images.  Backward: ``stem_pool_backward`` (-> u),
+    ``group_norm_backward`` with the prologue's mask (-> dy, dgamma, dbeta), ``stem_conv_weight_grad`` -- only what
+    ``needs_input_grad`` asks for.  The images are data: an x that requires grad raises ``ValueError``.  Fixed summation order, no
+    float atomics: the same bits on every run without ``torch.use_deterministic_algorithms``; no host wait, capturable."""
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.numel() == 0:
+        raise ValueError(f"stem_train: x must be a float32 (B, 3, L, W) batch with values, got {x.dtype} {tuple(x.shape)}")
+    if x.requires_grad:
+        raise ValueError("stem_train: x requires grad, and the stem has no input gradient (the images are data)")
+    if weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[1:]) != (3, 7, 7) or not 1 <= weight.shape[0] <= _STEM_MAX_OUT:
+        raise ValueError(f"stem_train: weight must be float32 (O <= {_STEM_MAX_OUT}, 3, 7, 7), got {weight.dtype} {tuple(weight.shape)}")
+    O = int(weight.shape[0])
+    if int(groups) < 1 or O % int(groups):
+        raise ValueError(f"stem_train: groups must divide O = {O}, got {groups}")
+    for t in (gamma, beta):
+        if t.dtype != torch.float32 or tuple(t.shape) != (O,):
+            raise ValueError(f"stem_train: a GroupNorm parameter must be float32 ({O},), got {t.dtype} {tuple(t.shape)}")
+    _lib.require_device(x, weight, gamma, beta)
+    return _StemTrain.apply(x, weight, gamma, beta, int(groups), float(eps))

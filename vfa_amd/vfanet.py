@@ -34,7 +34,14 @@ one autograd node per block that keeps three maps instead of the library's five 
 ``trunk_proj_train="hip"`` (independent of the three; default ``"library"``) runs the trunk's three projection blocks -- stride 2 and
 a 1 x 1 projection: the first block of ``layer2`` .. ``layer4`` -- WITH gradients on ``ops.projection_block_train``, one node per block
 that keeps four maps; the gradients of the stride-2 convolutions are ``vfa_trunk_down_wgrad_f32`` and ``vfa_trunk_down_dgrad_f32``
-(DESIGN.md 4.6).  With both training switches on ``"hip"`` only the stem runs as a module.
+(DESIGN.md 4.6).
+
+``trunk_stem_train="hip"`` (independent of the five; default ``"library"``) runs the trunk's stem WITH gradients on ``ops.stem_train``,
+one node that keeps the raw ``conv1`` map and the images -- no normalised map, no index map of the pooling; the backward is
+``vfa_stem_pool_backward_f32``, ``vfa_group_norm_backward_f32`` and ``vfa_stem_conv_wgrad_f32``.  The images are data: an
+input that requires grad takes the module stem.  With ``trunk_stem_train = trunk_convs_train = trunk_proj_train = "hip"`` no library
+convolution, normalisation or pooling runs in the trunk's forward or backward, and every trunk parameter's gradient is the same bits
+on every run without ``torch.use_deterministic_algorithms``; with only the latter two the stem runs as a module.
 """
 import glob
 import os
@@ -71,6 +78,8 @@ TRUNK_STEM = ("library", "hip")
 TRUNK_CONVS_TRAIN = ("library", "hip")
 # Who runs the trunk's projection blocks where gradients are enabled (``VFANet.trunk_proj_train``, ``VFANet.trunk``)
 TRUNK_PROJ_TRAIN = ("library", "hip")
+# Who runs the trunk's stem where gradients are enabled (``VFANet.trunk_stem_train``, ``VFANet.trunk``)
+TRUNK_STEM_TRAIN = ("library", "hip")
 
 
 def _find_pretrained(base):
@@ -199,6 +208,11 @@ class _Trunk(nn.Module):
         y = ops.stem_conv(x, self.conv1.weight)
         return ops.stem_pool(y, _gn_affine(y, self.bn1))
 
+    def stem_train_hip(self, x):
+        """``stem`` with gradients on ``ops.stem_train``: the calls of ``stem_hip`` and their bits, and a backward on the HIP kernels
+        from the raw map alone.  x is data (it must not require grad)."""
+        return ops.stem_train(x, self.conv1.weight, self.bn1.weight, self.bn1.bias, self.bn1.num_groups, self.bn1.eps)
+
     def stages(self, x):
         """``layer1`` .. ``layer4`` on the stem's output -> (f8, f16, f32)."""
         f8 = self.layer2(self.layer1(x))
@@ -255,6 +269,7 @@ class VFANet(nn.Module):
         self.trunk_stem = "library"  # or "hip" (``trunk``); the same kind of attribute, independent of ``trunk_convs``
         self.trunk_convs_train = "library"  # or "hip" (``trunk``, with gradients); the same kind of attribute, independent of both
         self.trunk_proj_train = "library"  # or "hip" (``trunk``, with gradients: the projection blocks); independent of the three
+        self.trunk_stem_train = "library"  # or "hip" (``trunk``, with gradients: the stem); independent of the five
         self.input_size = getattr(args, "resize_size", None)  # (H, W) uint8 frames are resized to (train.py:209-214); None: as they are
         self.base = _Trunk(_DEPTHS[base])
         if pretrained:
@@ -297,7 +312,11 @@ class VFANet(nn.Module):
         ``csrc/vfa_trunk_grad.hip``, ``_Trunk.stages_train_hip``; the stem and the projection blocks run as modules): it holds where
         gradients are enabled and ``x`` is a float32 CUDA tensor with at least one image, in training and in eval mode alike.
         ``trunk_proj_train`` names who runs the three projection blocks (the first of ``layer2`` .. ``layer4``) under the same
-        conditions (``"hip"``: ``ops.projection_block_train``); with both on ``"hip"`` only the stem runs as a module."""
+        conditions (``"hip"``: ``ops.projection_block_train``), and ``trunk_stem_train`` who runs the stem under them (``"hip"``:
+        ``ops.stem_train``, ``_Trunk.stem_train_hip``) -- with one further condition, that ``x`` does not require grad: the images are
+        data, and an input that does takes the module stem.  The training branch is taken when any of the three is ``"hip"``; with
+        all three no library convolution, normalisation or pooling runs in the trunk, forward or backward; with the stem's switch
+        on ``"library"`` the stem runs as a module."""
         if self.trunk_convs not in TRUNK_CONVS:
             raise ValueError(f"VFANet.trunk: trunk_convs is one of {TRUNK_CONVS}, got {self.trunk_convs!r}")
         if self.trunk_stem not in TRUNK_STEM:
@@ -310,9 +329,14 @@ class VFANet(nn.Module):
             return self.base.stages_hip(y) if self.trunk_convs == "hip" else self.base.stages(y)
         if self.trunk_proj_train not in TRUNK_PROJ_TRAIN:
             raise ValueError(f"VFANet.trunk: trunk_proj_train is one of {TRUNK_PROJ_TRAIN}, got {self.trunk_proj_train!r}")
-        if ("hip" in (self.trunk_convs_train, self.trunk_proj_train) and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
-                and x.dim() == 4 and x.numel() > 0):
-            return self.base.stages_train_hip(self.base.stem(x), self.trunk_convs_train == "hip", self.trunk_proj_train == "hip")
+        if self.trunk_stem_train not in TRUNK_STEM_TRAIN:
+            raise ValueError(f"VFANet.trunk: trunk_stem_train is one of {TRUNK_STEM_TRAIN}, got {self.trunk_stem_train!r}")
+        if ("hip" in (self.trunk_convs_train, self.trunk_proj_train, self.trunk_stem_train) and torch.is_grad_enabled() and x.is_cuda
+                and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0):
+            y = self.base.stem_train_hip(x) if self.trunk_stem_train == "hip" and not x.requires_grad else self.base.stem(x)
+            if "hip" not in (self.trunk_convs_train, self.trunk_proj_train):
+                return self.base.stages(y)
+            return self.base.stages_train_hip(y, self.trunk_convs_train == "hip", self.trunk_proj_train == "hip")
         return self.base(x)
 
     def laterals(self, images):
